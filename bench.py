@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the iSDF training hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of `Trainer.step`'s hot path (sampler -> fused PE+MLP chain
@@ -13,6 +13,10 @@ with 255-wide icosahedron PE, eikonal + normal terms on, bounds "ray".  With N
 ranks every rank draws its own 1000 rays (rays shard over ranks, weak scaling:
 N x 27k points per optimiser step) and ONE RCCL all-reduce carries the flat
 [grad | loss sums | bins] buffer.  Prints one JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline figures.  `--full` adds everything else the line
+has carried (pipelined and windowed rates, per-kernel times and rooflines, the CPU / eager-GPU baselines, the accuracy leg,
+the fp16 fast mode); `--dump-outputs DIR` writes what the last timed step computed as .npy files.
 """
 import argparse
 import ctypes
@@ -410,6 +414,12 @@ def main():
     ap.add_argument("--wide", action="store_true",
                     help="BASELINE configs[4] instead of the metric's configuration: hidden 512, 3 blocks (8 hidden layers), "
                          "n_freqs 10, 8000 rays = 216k points per GPU-step (not the reported bench line)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: pipelined and windowed rates, per-kernel times and rooflines, the CPU and eager-GPU "
+                         "baselines, the accuracy leg and the fp16 fast mode (minutes); a plain run times the K steps and stops")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (its losses, the parameters and AdamW moments "
+                         "it left, the keyframes' average losses) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -419,8 +429,9 @@ def main():
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        import subprocess
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -502,9 +513,10 @@ def main():
     K, W = args.steps, args.warmup
     # per-kernel HIP events ride on every PROF_EVERY-th timed step: four event records between the launches cost ~2 us of
     # stream time each (a step with them measured 305 us, without 296 us), and the other steps take the engine's cached call plan
+    # (--full only: a plain run times the steps alone)
     PROF_EVERY = 4
     KP = max(K // PROF_EVERY, 1)             # on the LAST step of every group of four (never the first step behind the barrier)
-    events = HipEvents(4 * KP)
+    events = HipEvents(4 * KP) if args.full else None
 
     overlap = group is not None and args.overlap_allreduce
     split_ev, side = (dp.new_split_event(dev), torch.cuda.Stream(dev)) if overlap else (None, None)
@@ -538,6 +550,9 @@ def main():
     # FIRST process on a freshly booted box stalls one step for ~35-40 ms about half a second into its run (seen three times in
     # round 3, never in a second process) -- the ramp is longer than that
     tr.noise_std = tr.noise_kf
+    # the ramp trains too, for a number of steps that depends on the box: its steps are undone afterwards (the trainer's own
+    # checkpoint / resume, exact), so that the warm-up and timed steps start from the seeded initial state on every run
+    initial_state = tr.state_dict()
     ramp_steps, t_r = 0, time.perf_counter()
     if group is None:
         while time.perf_counter() - t_r < args.ramp_seconds:
@@ -547,7 +562,10 @@ def main():
         for _ in range(int(1000 * args.ramp_seconds)):
             tr.step(); ramp_steps += 1
     torch.cuda.synchronize()
-    events.prime(torch.cuda.current_stream(dev).cuda_stream)
+    tr.load_state_dict(initial_state)
+    del initial_state
+    if events is not None:
+        events.prime(torch.cuda.current_stream(dev).cuda_stream)
     for i in range(W):
         tr.step()
     torch.cuda.synchronize()
@@ -559,10 +577,10 @@ def main():
     per_step = np.empty(K)
     t0 = time.perf_counter()
     for i in range(K):
-        if (i % PROF_EVERY == PROF_EVERY - 1 or K < PROF_EVERY and i == K - 1) and i // PROF_EVERY < KP:
+        if events is not None and (i % PROF_EVERY == PROF_EVERY - 1 or K < PROF_EVERY and i == K - 1) and i // PROF_EVERY < KP:
             tr._hip.prof_events = events.group(i // PROF_EVERY)       # HIP events around this step's kernels, on the launch stream
         t_a = time.perf_counter()
-        tr.step()
+        last = tr.step()
         per_step[i] = time.perf_counter() - t_a
     torch.cuda.synchronize()
     if group is not None:
@@ -574,6 +592,49 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     sync_step_ms = 1e3 * elapsed / K
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, last[0])
+
+    batches = world if (args.scaling == "weak" or world == 1) else 1
+    res = {
+        "metric": "train-steps/sec: device-synchronised Trainer.step() on 27k-point ray batches, timed as metrics.start_timing / end_timing bracket it (SURVEY 8d); whole job.  SDF L1 vs GT: sdf_l1_vs_gt",
+        # weak: N x 27k points per optimiser step = N batches; strong: ONE 27k-point batch per optimiser step whatever N
+        "value": round(batches * K / elapsed, 2),
+        "unit": "train-steps/s",
+        "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": round(1e3 * elapsed / K, 4),
+        "higher_is_better": True,
+        "scaling": args.scaling if world > 1 else "weak",
+        "vs_baseline": None,
+        "distributed": {"world_size": torch.distributed.get_world_size() if group is not None else 1,
+                        "backend": torch.distributed.get_backend() if group is not None else None,
+                        "collectives_per_step": 0 if group is None else (2 if overlap else 1),
+                        "overlap_allreduce": bool(overlap), "collective": getattr(tr._hip, "collective", None)},
+        "dtype": {"fp16x2": "f16 MFMA operands (compensated forward: hi+lo operands past the cat layer), f32 accumulate; ",
+                  "fp16x2_full": "f16 MFMA operands (exact-forward instrument: hi+lo operands in every forward layer), f32 accumulate; ",
+                  "fp16": "f16 MFMA operands, f32 accumulate; ", "bf16": "bf16 MFMA operands, f32 accumulate; "}[args.fwd_operand]
+                 + "second-order sweeps and dW operands %s" % (eng.net.bwd_operand or ("bf16" if args.fwd_operand == "bf16" else "fp16")),
+        "fwd_operand": args.fwd_operand, "bwd_operand": eng.net.bwd_operand or ("bf16" if args.fwd_operand == "bf16" else "fp16"),
+        "data": "synthetic",
+        "config": {"workload": ("replicaCAD.json defaults: 5 keyframes x %d rays x 27 samples = %d points per "
+                                "rank-step, STREAM synthetic room depth, 6x256 Softplus MLP + 255-wide "
+                                "icosahedron PE (460033 params), eik+normal loss, bounds=ray, AdamW"
+                                if not args.wide else
+                                "BASELINE configs[4] (wide): 5 keyframes x %d rays x 27 samples = %d points per "
+                                "rank-step, STREAM synthetic room depth, 8x512 Softplus MLP + 423-wide "
+                                "icosahedron PE (2272769 params), eik+normal loss, bounds=ray, AdamW")
+                               .replace("STREAM", "%dx%d" % (cam["H"], cam["W"])) % (sc.n_rays, max_rays * S),
+                   "stream": "%dx%d" % (cam["H"], cam["W"]),
+                   "global_points_per_step": int(world * max_rays * S),
+                   "scaling_mode": ("weak: every rank draws the full 5 x 200 rays" if args.scaling == "weak" or world == 1 else
+                                    "strong: the 27k-point batch split over %d ranks (%d rays per keyframe and rank)" % (world, sc.n_rays)),
+                   "parallelism": "dp%d (rays sharded, one %s all-reduce of %d floats)"
+                                  % (world, "RCCL" if backend == "nccl" else backend, eng.reduce_buf.numel())
+                   if world > 1 else "single GPU"},
+        "clock_ramp": {"untimed_steps_before_warmup": ramp_steps, "seconds": args.ramp_seconds},
+    }
+    if not args.full:
+        return finish(res, group, rank)
 
     # ---- informational: the same step PIPELINED (K2 steps between two synchronisations, the engine called directly: no timing
     # bracket, no loss dict) -- what the device can do when the host never waits; rounds 1-5 reported this as `value`
@@ -679,7 +740,6 @@ def main():
                           "valu_instructions_per_mfma": ck["valu_instructions_per_mfma"],
                           "valu_cycles_per_instruction": ck["valu_cycles_per_instruction"],
                           "source": os.path.relpath(ipath, ROOT), "model": ij.get("model")}
-    batches = world if (args.scaling == "weak" or world == 1) else 1
     per_rank_chain_us, per_rank_elapsed = [round(t_chain * 1e6, 1)], [round(my_elapsed, 4)]
     if group is not None:      # every rank's own chain-kernel time and wall clock in the line (rank 0 prints)
         slots = torch.zeros(2 * world, dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -689,43 +749,8 @@ def main():
         per_rank_elapsed = [round(float(v), 4) for v in slots[1::2]]
     if rank == 0:
         flops_chain = 8.0 * m_mac * P      # fwd 2M + input-grad 2M + its adjoint 2M + reverse sweep 2M
-        res = {
-            "metric": "train-steps/sec: device-synchronised Trainer.step() on 27k-point ray batches, timed as metrics.start_timing / end_timing bracket it (SURVEY 8d); whole job.  SDF L1 vs GT: sdf_l1_vs_gt",
-            # weak: N x 27k points per optimiser step = N batches; strong: ONE 27k-point batch per optimiser step whatever N
-            "value": round(batches * K / elapsed, 2),
-            "unit": "train-steps/s",
-            "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": round(1e3 * elapsed / K, 4),
-            "higher_is_better": True,
-            "scaling": args.scaling if world > 1 else "weak",
-            "vs_baseline": None,
-            "distributed": {"world_size": torch.distributed.get_world_size() if group is not None else 1,
-                            "backend": torch.distributed.get_backend() if group is not None else None,
-                            "collectives_per_step": 0 if group is None else (2 if overlap else 1),
-                            "overlap_allreduce": bool(overlap), "collective": getattr(tr._hip, "collective", None),
-                            "per_rank_chain_us": per_rank_chain_us,
-                            "per_rank_elapsed_s": per_rank_elapsed},
-            "dtype": {"fp16x2": "f16 MFMA operands (compensated forward: hi+lo operands past the cat layer), f32 accumulate; ",
-                      "fp16x2_full": "f16 MFMA operands (exact-forward instrument: hi+lo operands in every forward layer), f32 accumulate; ",
-                      "fp16": "f16 MFMA operands, f32 accumulate; ", "bf16": "bf16 MFMA operands, f32 accumulate; "}[args.fwd_operand]
-                     + "second-order sweeps and dW operands %s" % (eng.net.bwd_operand or ("bf16" if args.fwd_operand == "bf16" else "fp16")),
-            "fwd_operand": args.fwd_operand, "bwd_operand": eng.net.bwd_operand or ("bf16" if args.fwd_operand == "bf16" else "fp16"),
-            "data": "synthetic",
-            "config": {"workload": ("replicaCAD.json defaults: 5 keyframes x %d rays x 27 samples = %d points per "
-                                    "rank-step, STREAM synthetic room depth, 6x256 Softplus MLP + 255-wide "
-                                    "icosahedron PE (460033 params), eik+normal loss, bounds=ray, AdamW"
-                                    if not args.wide else
-                                    "BASELINE configs[4] (wide): 5 keyframes x %d rays x 27 samples = %d points per "
-                                    "rank-step, STREAM synthetic room depth, 8x512 Softplus MLP + 423-wide "
-                                    "icosahedron PE (2272769 params), eik+normal loss, bounds=ray, AdamW")
-                                   .replace("STREAM", "%dx%d" % (cam["H"], cam["W"])) % (sc.n_rays, max_rays * S),
-                       "stream": "%dx%d" % (cam["H"], cam["W"]),
-                       "global_points_per_step": int(world * max_rays * S),
-                       "scaling_mode": ("weak: every rank draws the full 5 x 200 rays" if args.scaling == "weak" or world == 1 else
-                                        "strong: the 27k-point batch split over %d ranks (%d rays per keyframe and rank)" % (world, sc.n_rays)),
-                       "parallelism": "dp%d (rays sharded, one %s all-reduce of %d floats)"
-                                      % (world, "RCCL" if backend == "nccl" else backend, eng.reduce_buf.numel())
-                       if world > 1 else "single GPU"},
+        res["distributed"].update(per_rank_chain_us=per_rank_chain_us, per_rank_elapsed_s=per_rank_elapsed)
+        res.update({
             "points_per_s": round(world * P * K / elapsed, 1),
             "valid_points_per_step": round(P, 1),
             "final_total_loss": round(final_loss, 5),
@@ -752,7 +777,6 @@ def main():
                         "synchronising copy per step); the window goes to the kernels inline",
                 "frame_avg_losses_placement_ab": losses_ab,
                 "window_transport_ab": transport_ab},
-            "clock_ramp": {"untimed_steps_before_warmup": ramp_steps, "seconds": args.ramp_seconds},
             "chain_us_per_step": {"first5": [round(float(v), 1) for v in chain_us[:5]], "min": round(float(chain_us.min()), 1),
                                   "median": round(float(np.median(chain_us)), 1), "max": round(float(chain_us.max()), 1),
                                   "launches_timed": int(KP), "what": "HIP events around the chain kernel on every %d-th timed step" % PROF_EVERY},
@@ -779,7 +803,7 @@ def main():
                          "algorithmic_flop_per_launch": flops_chain,
                          "issue_port": issue_port,
                          "whole_step_frac_of_mfma_peak": round(12.0 * m_mac * P * K / elapsed / MFMA_PEAK, 5)},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg, args.cpu_threads)
             res["speedup_vs_cpu_baseline"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
@@ -814,6 +838,23 @@ def main():
                                      "chain_ms": round(c2 * 1e3, 4), "chain_frac_of_mfma_peak": round(flops_chain / c2 / MFMA_PEAK, 5),
                                      "what": "fwd_operand=fp16 (no compensation GEMMs); parity: sdf rel-L2 0.9e-3 .. 1.5e-3 vs the "
                                              "reference at BASELINE size, i.e. NOT within the north star's 1e-3 on every fixture"}
+    finish(res, group, rank)
+
+
+def dump_outputs(d, tr, losses):
+    """What the last timed step computed, as a caller of Trainer.step() receives it: the returned losses (float64) and the state the
+    step's update left behind -- network parameters, AdamW moments, the keyframes' average losses (float32, flat)."""
+    os.makedirs(d, exist_ok=True)
+    eng = tr.engine
+    out = {k: np.array([float(v)], dtype=np.float64) for k, v in losses.items()}
+    for k, t in (("params", eng.params), ("exp_avg", eng.exp_avg), ("exp_avg_sq", eng.exp_avg_sq),
+                 ("frame_avg_losses", tr.frames.frame_avg_losses)):
+        out[k] = t.detach().reshape(-1).float().cpu().numpy()
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
+def finish(res, group, rank):
     if group is not None:
         torch.distributed.destroy_process_group()
     try:      # RCCL prints its version banner through C stdio, which is flushed at exit when stdout is a pipe:

@@ -102,6 +102,9 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise IsdfError("%s not found: run `python -m isdf_amd.build` (or __graft_entry__.build())"
                         % LIB_PATH)
+    # torch first: its bundled HIP runtime then answers the library's libamdhip64.so.7 as well.  Loaded the other way round, the
+    # process holds two HIP runtimes (torch asks for the unversioned name), and the library's own finds no device next to torch's.
+    import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
     P, i32, i64, f32, vp = C.POINTER, C.c_int32, C.c_int64, C.c_float, C.c_void_p
     L.isdf_abi_version.restype = C.c_int

@@ -49,7 +49,7 @@ if [ "$stage" = ab1 ]; then
   python -m pytest tests/test_gpu_parity.py -q -s -m gpu -k "trained" > $O/pytest_trained.log 2>&1; lap pytest trained
   python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; lap pytest gpu
   for rep in 1 2; do for f in variants/lib_*.so; do
-    ISDF_HIP_LIB=$PWD/$f python bench.py --steps 300 --warmup 50 --no-cpu-baseline > $O/ab1_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
+    ISDF_HIP_LIB=$PWD/$f python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline > $O/ab1_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
   done; done
   python tests/accuracy_experiment.py --native-clock --backend hip --seeds 1 2 --out $O/native_clock_hip_diag.json > $O/native_clock_hip_diag.log 2>&1; lap native diag
   python tests/accuracy_experiment.py --backend hip --seeds $(seq 11 40) --keyframes 24 --steps-per-kf 100 \
@@ -73,19 +73,19 @@ if [ "$stage" = ab2 ]; then
   ISDF_HIP_LIB=$PWD/variants/lib_biaslds2.so python -m pytest tests/test_gpu_parity.py -q -m gpu \
       -k "ragged or base_size_forward or public_seams or determinism or checkpoint or trained" > $O/pytest_biaslds2.log 2>&1; lap pytest biaslds2
   for rep in 1 2; do for f in variants/lib_*.so; do
-    ISDF_HIP_LIB=$PWD/$f python bench.py --steps 300 --warmup 50 --no-cpu-baseline > $O/ab2_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
+    ISDF_HIP_LIB=$PWD/$f python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline > $O/ab2_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
   done; done
   S20="$(seq 1 20)"
   python tests/accuracy_experiment.py --paired-draws --backend hip --seeds $S20 --keyframes 24 --steps-per-kf 100 \
       --out $O/acc_paired_hip.json > $O/acc_paired_hip.log 2>&1; lap paired hip
   python tests/accuracy_experiment.py --paired-draws --backend port --device cuda --seeds $S20 --keyframes 24 --steps-per-kf 100 \
       --out $O/acc_paired_control.json > $O/acc_paired_control.log 2>&1; lap paired control
-  ISDF_BENCH_FORCE_DP=1 python bench.py --steps 300 --warmup 50 --no-cpu-baseline > $O/bench_forced_dp_world1.json 2> $O/bench_forced_dp_world1.err; lap dp1
-  ISDF_BENCH_FORCE_DP=1 python bench.py --steps 300 --warmup 50 --no-cpu-baseline --overlap-allreduce > $O/bench_forced_dp_world1_overlap.json 2> $O/bench_forced_dp_world1_overlap.err; lap dp1 overlap
+  ISDF_BENCH_FORCE_DP=1 python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline > $O/bench_forced_dp_world1.json 2> $O/bench_forced_dp_world1.err; lap dp1
+  ISDF_BENCH_FORCE_DP=1 python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline --overlap-allreduce > $O/bench_forced_dp_world1_overlap.json 2> $O/bench_forced_dp_world1_overlap.err; lap dp1 overlap
   for mode in "--scaling weak" "--scaling strong" "--scaling weak --overlap-allreduce"; do
     tag=$(echo $mode | tr -d ' -')
     ISDF_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 \
-        bench.py --gpus 2 --steps 100 --warmup 20 --no-cpu-baseline $mode > $O/bench_dp2_gloo_$tag.json 2> $O/bench_dp2_gloo_$tag.err; lap dp2 $tag
+        bench.py --full --gpus 2 --steps 100 --warmup 20 --no-cpu-baseline $mode > $O/bench_dp2_gloo_$tag.json 2> $O/bench_dp2_gloo_$tag.err; lap dp2 $tag
   done
   tail -n 12 $O/pytest_gpu2.log; tail -n 6 $O/pytest_biaslds2.log
   grep -h "trained-weights eval\|worst tensor\|trained-state" $O/pytest_gpu2.log | cut -c1-900
@@ -121,7 +121,7 @@ fi
 if [ "$stage" = bwd16 ]; then
   python -m pytest tests -q -m gpu -s > $O/pytest_gpu_bwd16.log 2>&1; lap pytest gpu
   for rep in 1 2; do for b in bf16 fp16; do
-    python bench.py --steps 300 --warmup 50 --no-cpu-baseline --bwd-operand $b > $O/ab3_bwd_${b}_$rep.json 2> /dev/null; lap bench $b $rep
+    python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline --bwd-operand $b > $O/ab3_bwd_${b}_$rep.json 2> /dev/null; lap bench $b $rep
   done; done
   for b in fp16 bf16; do
     python tests/accuracy_experiment.py --backend hip --seeds $(seq 1 40) --keyframes 24 --steps-per-kf 100 --bwd-operand $b \
@@ -145,11 +145,11 @@ if [ "$stage" = final2 ]; then      # the records of the FINAL tree (fp16 second
   bash tools/round_records.sh 04 > $O/round_records2.log 2>&1; lap records
   cd $GRAFT_REPO_ROOT
   python tests/accuracy_experiment.py --native-clock --backend hip --seeds $SEEDS5 --out $O/native_clock_hip_final2.json > $O/native_clock_hip_final2.log 2>&1; lap native hip
-  ISDF_BENCH_FORCE_DP=1 python bench.py --steps 300 --warmup 50 --no-cpu-baseline --overlap-allreduce 2> /dev/null | tail -1 > $O/bench_forced_dp_world1_overlap_final.json; lap dp1 overlap
+  ISDF_BENCH_FORCE_DP=1 python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline --overlap-allreduce 2> /dev/null | tail -1 > $O/bench_forced_dp_world1_overlap_final.json; lap dp1 overlap
   for mode in "--scaling weak" "--scaling strong" "--scaling weak --overlap-allreduce"; do
     tag=$(echo $mode | tr -d ' -')
     ISDF_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 \
-        bench.py --gpus 2 --steps 100 --warmup 20 --no-cpu-baseline $mode 2> /dev/null | tail -1 > $O/bench_dp2_gloo_final_$tag.json; lap dp2 $tag
+        bench.py --full --gpus 2 --steps 100 --warmup 20 --no-cpu-baseline $mode 2> /dev/null | tail -1 > $O/bench_dp2_gloo_final_$tag.json; lap dp2 $tag
   done
   tail -n 6 $O/pytest_gpu_final2.log
   tail -n 45 $O/round_records2.log
@@ -166,7 +166,7 @@ if [ "$stage" = hidden ]; then
   grep "sdf (scaled\|passed\|failed" $O/pytest_narrow.log
   timeout 600 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; lap "pytest gpu rc=$?"
   tail -5 $O/pytest_gpu.log
-  timeout 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err; lap bench
+  timeout 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; lap bench
   cat $O/bench.json
 fi
 
@@ -190,7 +190,7 @@ if [ "$stage" = pinned ]; then
   cat $O/pk_fma_opsel.txt
   timeout 300 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "pinned_host or trainer_step_contract or checkpoint or driver_schedule" > $O/pytest_pinned.log 2>&1; lap "pytest rc=$?"
   tail -4 $O/pytest_pinned.log
-  timeout 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err; lap bench
+  timeout 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; lap bench
   python - <<'PY'
 import json
 j = json.loads(open("gpurun_out/r04pinned/bench.json").read().strip().split("\n")[-1])

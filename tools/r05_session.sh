@@ -29,7 +29,7 @@ if [ "$stage" = fwd1 ]; then
   timeout 900 python -m pytest tests -q -m gpu -x > $O/pytest_gpu.log 2>&1; lap pytest rc=$?
   timeout 600 python bench.py --infer-points 8000000 > $O/bench_infer.json 2> $O/bench_infer.err; lap bench infer
   ISDF_HIP_LIB=$PWD/variants/lib_onetile.so timeout 600 python bench.py --infer-points 8000000 > $O/bench_infer_onetile.json 2> /dev/null; lap bench infer onetile
-  timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; lap bench
+  timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; lap bench
   tail -n 4 $O/check_pair.log $O/check_onetile.log; tail -n 40 $O/compare.log; tail -n 5 $O/pytest_gpu.log
   head -c 1500 $O/bench_infer.json; echo; head -c 600 $O/bench_infer_onetile.json; echo
   cat $O/timeline_fp16.txt | tail -n 45
@@ -58,7 +58,7 @@ if [ "$stage" = fwd3 ]; then
   ISDF_FWD_OPERAND=fp16x2 timeout 300 python tools/timeline_fwd.py > $O/timeline_fp16x2.txt 2>&1; lap timeline fp16x2
   timeout 900 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; lap pytest rc=$?
   timeout 600 python bench.py --infer-points 8000000 > $O/bench_infer.json 2> $O/bench_infer.err; lap bench infer
-  timeout 900 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err; lap bench
+  timeout 900 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; lap bench
   tail -n 4 $O/check_pair.log $O/check_onetile.log; grep -c "bit-identical" $O/compare.log; grep "DIFFERENT" $O/compare.log | head -20; tail -n 1 $O/compare.log
   tail -n 32 $O/timeline_fp16.txt; tail -n 15 $O/timeline_fp16x2.txt; tail -n 12 $O/pytest_gpu.log
   python - "$O/bench.json" <<'PY'
@@ -85,7 +85,7 @@ if [ "$stage" = chain1 ]; then
   ISDF_HIP_LIB=$PWD/variants/lib_prev.so timeout 300 python tools/train_ab_check.py --dump /tmp/tb.npz > $O/ab_dump_prev.log 2>&1; lap dump prev rc=$?
   python tools/train_ab_check.py --compare /tmp/ta.npz /tmp/tb.npz > $O/ab_compare.log 2>&1; lap compare
   for rep in 1 2; do for f in variants/lib_prev.so isdf_amd/libisdf_hip.so; do
-    ISDF_HIP_LIB=$PWD/$f timeout 300 python bench.py --steps 300 --warmup 50 --no-cpu-baseline > $O/ab_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
+    ISDF_HIP_LIB=$PWD/$f timeout 300 python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline > $O/ab_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
   done; done
   timeout 300 python tools/timeline.py > $O/timeline_train.txt 2>&1; lap timeline
   timeout 900 python -m pytest tests -q -m gpu -s > $O/pytest_gpu.log 2>&1; lap pytest rc=$?
@@ -115,7 +115,7 @@ if [ "$stage" = tp1 ]; then      # pair-tile train kernel: outputs of one step a
   python tools/train_ab_check.py --compare /tmp/ta.npz /tmp/tb.npz > $O/ab_compare.log 2>&1; lap compare
   cat $O/ab_compare.log; tail -n 3 $O/ab_dump_new.log
   for f in variants/lib_prev.so isdf_amd/libisdf_hip.so; do
-    ISDF_HIP_LIB=$PWD/$f timeout 300 python bench.py --steps 300 --warmup 50 --no-cpu-baseline > $O/ab_$(basename $f .so).json 2> $O/ab_$(basename $f .so).err; lap bench $f
+    ISDF_HIP_LIB=$PWD/$f timeout 300 python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline > $O/ab_$(basename $f .so).json 2> $O/ab_$(basename $f .so).err; lap bench $f
   done
   for f in $O/ab_lib*.json; do python - "$f" <<'PY'
 import json, sys
@@ -133,7 +133,7 @@ fi
 if [ "$stage" = tp2 ]; then      # pair-tile train kernel: stage timeline (variants/lib_dbg.so) + bench
   timeout 300 python tools/timeline.py > $O/timeline_train.txt 2>&1; lap timeline
   ISDF_FWD_OPERAND=fp16 timeout 300 python tools/timeline.py > $O/timeline_train_fp16.txt 2>&1; lap timeline fp16
-  timeout 300 python bench.py --steps 300 --warmup 50 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; lap bench
+  timeout 300 python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; lap bench
   cat $O/timeline_train.txt | head -130; tail -n 8 $O/timeline_train.txt
   python - "$O/bench.json" <<'PY'
 import json, sys
@@ -144,7 +144,7 @@ fi
 
 if [ "$stage" = tp3 ]; then      # pair-tile train kernel variants: cache policy of the spill traffic, epilogue groups late in the stage
   for rep in 1 2; do for f in variants/lib_prev.so isdf_amd/libisdf_hip.so variants/lib_tpdef.so variants/lib_tplate.so; do
-    ISDF_HIP_LIB=$PWD/$f timeout 300 python bench.py --steps 300 --warmup 50 --no-cpu-baseline > $O/ab_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
+    ISDF_HIP_LIB=$PWD/$f timeout 300 python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline > $O/ab_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
   done; done
   for f in $O/ab_lib*.json; do python - "$f" <<'PY'
 import json, sys
@@ -164,7 +164,7 @@ if [ "$stage" = tp4 ]; then      # pair-tile train kernel: check vs prev + bench
   ISDF_HIP_LIB=$PWD/variants/lib_prev.so timeout 300 python tools/train_ab_check.py --dump /tmp/tb.npz > $O/ab_dump_prev.log 2>&1; lap dump prev rc=$?
   python tools/train_ab_check.py --compare /tmp/ta.npz /tmp/tb.npz > $O/ab_compare.log 2>&1; head -n 8 $O/ab_compare.log
   for rep in 1 2; do for f in variants/lib_prev.so isdf_amd/libisdf_hip.so; do
-    ISDF_HIP_LIB=$PWD/$f timeout 300 python bench.py --steps 300 --warmup 50 --no-cpu-baseline > $O/ab_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
+    ISDF_HIP_LIB=$PWD/$f timeout 300 python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline > $O/ab_$(basename $f .so)_$rep.json 2> /dev/null; lap bench $f $rep
   done; done
   for f in $O/ab_lib*.json; do python - "$f" <<'PY'
 import json, sys
