@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ISDF_ABI_VERSION 7
+#define ISDF_ABI_VERSION 8
 
 enum {
   ISDF_OK = 0,
@@ -373,6 +373,53 @@ int isdf_adamw(const isdf_net_cfg* net, float* params, float* exp_avg, float* ex
                const float* grad_sum, const float* count_ptr, float grad_scale,
                float lr, float beta1, float beta2, float eps, float weight_decay,
                int32_t step, void* shadow, void* stream);
+
+/* ---- mesh reconstruction (ABI 8) -------------------------------------------
+ * Marching cubes over a dense fp32 volume, the isosurface step of
+ * Trainer.mesh_rec (trainer.py:1500-1542; draw3D.marching_cubes_trimesh,
+ * draw3D.py:111-160).  An INDEXED mesh: one vertex per sign-changing grid edge.
+ *   - corner inside iff value < level (a value equal to level is outside);
+ *   - a cell with a non-finite corner emits no triangle, an edge with a
+ *     non-finite end no vertex (so no face references a missing vertex);
+ *   - grid point (i,j,k) owns its +i, +j, +k edges; vertices are ordered by the
+ *     owner's linear index, then axis (i < j < k); faces by cell linear index,
+ *     then table order: the output is bit-reproducible (no atomics decide it);
+ *   - vertex = a + t (b - a), t = (level - f(a)) / (f(b) - f(a)), in index
+ *     coordinates; normal = the central-difference gradient (one-sided at the
+ *     borders) interpolated with the same t and normalised: it points toward
+ *     increasing value, and the right-hand normal of every face agrees;
+ *   - has_transform: positions go through index_to_world (rows of a 3x4
+ *     affine), normals through the inverse transpose of its 3x3 part and are
+ *     renormalised (a singular 3x3 part: ISDF_EINVAL).                         */
+typedef struct isdf_mc_args {
+  const float* volume;        /* [D0][D1][D2] row-major: vol[i][j][k]                    */
+  int32_t D0, D1, D2;         /* each >= 2, D0*D1*D2 <= 2^31 - 1                         */
+  float level;
+  int32_t has_transform;
+  float index_to_world[12];   /* rows of the 3x4 affine (used iff has_transform)         */
+} isdf_mc_args;
+
+#define ISDF_MC_MAX_TRIS 5    /* triangles per cell; isdf_mc_tables' row width is 3x this */
+
+/* workspace bytes of isdf_marching_cubes for a D0 x D1 x D2 volume (ISDF_EINVAL outside the bounds above) */
+int64_t isdf_mesh_ws_bytes(int32_t D0, int32_t D1, int32_t D2);
+
+/* counts: device int64[2] = (vertices, faces), ALWAYS written.  verts / normals
+ * [max_verts][3] fp32 and faces [max_faces][3] int32 (vertex ids) are written
+ * only when the whole mesh fits (vertices <= max_verts, faces <= max_faces);
+ * otherwise read counts and call again with larger buffers.  normals may be
+ * NULL.  Four launches on `stream`; the workspace needs no initialisation.   */
+int isdf_marching_cubes(const isdf_mc_args* args, int64_t* counts, float* verts, float* normals,
+                        int64_t max_verts, int32_t* faces, int64_t max_faces, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
+/* HOST-only copy of the tables the kernels use (launches nothing; either
+ * pointer may be NULL): edge_corners_host int32[12][2] -- edge e runs along
+ * axis e / 4 from corner [e][0] to corner [e][1], corner c sitting at offset
+ * (c & 1, c >> 1 & 1, c >> 2 & 1) -- and tri_table_host int8[256][3 *
+ * ISDF_MC_MAX_TRIS]: the edge triples of case c (bit c set = corner c inside),
+ * -1 padded.                                                                  */
+int isdf_mc_tables(int32_t* edge_corners_host, int8_t* tri_table_host);
 
 #ifdef __cplusplus
 }

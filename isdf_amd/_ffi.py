@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # ISDF_HIP_LIB: development override (A/B variants and the instrumented build of tools/build_variants.py)
 LIB_PATH = os.environ.get("ISDF_HIP_LIB") or os.path.join(HERE, "libisdf_hip.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # every symbol include/isdf_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -20,7 +20,9 @@ SYMBOLS = [
     "isdf_sample_rays",
     "isdf_sdf_eval", "isdf_train_step", "isdf_train_step_adamw", "isdf_train_step_finish", "isdf_bounds_pc",
     "isdf_frame_avg", "isdf_adamw", "isdf_estimate_normals", "isdf_render_depth", "isdf_allreduce_sum_f32",
+    "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables",
 ]
+MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
 LS_SDF, LS_GRAD, LS_EIK, LS_TOTAL, LS_COUNT = 0, 1, 2, 3, 4
 
@@ -86,6 +88,11 @@ class OptimArgs(C.Structure):
 MAX_INLINE_FRAMES = 8
 
 
+class McArgs(C.Structure):
+    _fields_ = [("volume", C.c_void_p), ("D0", C.c_int32), ("D1", C.c_int32), ("D2", C.c_int32), ("level", C.c_float),
+                ("has_transform", C.c_int32), ("index_to_world", C.c_float * 12)]
+
+
 
 class IsdfError(RuntimeError):
     pass
@@ -133,8 +140,12 @@ def lib():
     L.isdf_adamw.argtypes = [P(NetCfg), vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp]
     L.isdf_estimate_normals.argtypes = [vp, i32, i32, f32, f32, f32, f32, vp, vp]
     L.isdf_render_depth.argtypes = [vp, i64, i64, i32, vp, vp, vp, f32, vp, vp, vp]
+    L.isdf_mesh_ws_bytes.argtypes = [i32, i32, i32]
+    L.isdf_marching_cubes.argtypes = [P(McArgs), vp, vp, vp, i64, vp, i64, vp, i64, vp]
+    L.isdf_mc_tables.argtypes = [vp, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
+    L.isdf_mesh_ws_bytes.restype = i64
     if L.isdf_abi_version() != ABI_VERSION:
         raise IsdfError("libisdf_hip.so ABI %d != binding ABI %d" % (L.isdf_abi_version(), ABI_VERSION))
     _lib = L

@@ -37,6 +37,11 @@ int launch_normals(const float* depth, int H, int W, float fx, float fy, float c
 int launch_render_depth(const int32_t* n_valid, int64_t n_host, int64_t max_rays, int S, const float* z,
                         const float* sdf, const float* depth_sample, float th, float* view, int32_t* below,
                         hipStream_t st);
+int64_t mesh_ws_layout(int64_t P, int64_t* nBlocks, int64_t* offOff, int64_t* offTot, int64_t* offVbase);
+int launch_marching_cubes(const float* vol, int32_t D0, int32_t D1, int32_t D2, float level, const float* A, const float* N,
+                          int64_t* counts, float* verts, float* normals, int64_t max_verts, int32_t* faces, int64_t max_faces,
+                          void* workspace, hipStream_t st);
+void mc_tables_host(int32_t* edge_corners, int8_t* tri_table);
 }  // namespace isdf
 
 namespace isdf { thread_local int g_isdf_last_hip_error = 0; }
@@ -342,6 +347,45 @@ int isdf_adamw(const isdf_net_cfg* net, float* params, float* exp_avg, float* ex
                     step, l.n_params, (hipStream_t)stream);
   if (rc || !shadow) return rc;
   return launch_pack(l, params, (uint16_t*)shadow, (hipStream_t)stream);
+}
+
+static bool mesh_dims_ok(int32_t D0, int32_t D1, int32_t D2) {
+  return D0 >= 2 && D1 >= 2 && D2 >= 2 && (int64_t)D0 * D1 * D2 <= 0x7fffffff;
+}
+
+int64_t isdf_mesh_ws_bytes(int32_t D0, int32_t D1, int32_t D2) {
+  if (!mesh_dims_ok(D0, D1, D2)) return ISDF_EINVAL;
+  return mesh_ws_layout((int64_t)D0 * D1 * D2, nullptr, nullptr, nullptr, nullptr);
+}
+
+int isdf_marching_cubes(const isdf_mc_args* a, int64_t* counts, float* verts, float* normals, int64_t max_verts,
+                        int32_t* faces, int64_t max_faces, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!a || !a->volume || !counts || !mesh_dims_ok(a->D0, a->D1, a->D2) || max_verts < 0 || max_faces < 0) return ISDF_EINVAL;
+  if ((max_verts > 0 && !verts) || (max_faces > 0 && !faces)) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_mesh_ws_bytes(a->D0, a->D1, a->D2)) return ISDF_EWORKSPACE;
+  float N[9];
+  if (a->has_transform) {   // normals: inverse transpose of the affine's 3x3 part (cofactor matrix / determinant)
+    const float* m = a->index_to_world;
+    auto M = [m](int r, int c) { return (double)m[4 * r + c]; };
+    double cof[9];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+        cof[3 * r + c] = M(r1, c1) * M(r2, c2) - M(r1, c2) * M(r2, c1);
+      }
+    const double det = M(0, 0) * cof[0] + M(0, 1) * cof[1] + M(0, 2) * cof[2];
+    if (!(det != 0.0) || !__builtin_isfinite(det)) return ISDF_EINVAL;
+    for (int q = 0; q < 9; ++q) N[q] = (float)(cof[q] / det);   // (A^-1)^T = cof(A) / det(A)
+  }
+  return launch_marching_cubes(a->volume, a->D0, a->D1, a->D2, a->level, a->has_transform ? a->index_to_world : nullptr,
+                               a->has_transform ? N : nullptr, counts, verts, normals, max_verts, faces, max_faces, workspace,
+                               (hipStream_t)stream);
+}
+
+int isdf_mc_tables(int32_t* edge_corners_host, int8_t* tri_table_host) {
+  mc_tables_host(edge_corners_host, tri_table_host);
+  return ISDF_OK;
 }
 
 }  // extern "C"

@@ -199,6 +199,7 @@ class Engine:
         self._ws = None
         self._ws_key = None
         self._scan_ws = None      # sampler look-back state (zero on first use, self re-arming afterwards)
+        self._mesher = None       # marching-cubes workspace, count pair and output capacity (isdf_amd.mesh.Mesher)
         self.reduce_buf = None
         self.reduce_extra = 0
         self.reduce_floats = 0
@@ -612,6 +613,16 @@ class Engine:
                                               _ffi.ptr(sdf.contiguous()), _ffi.ptr(depth_sample), float(kf_dist_th),
                                               _ffi.ptr(view), _ffi.ptr(below), _stream(self.device)), "isdf_render_depth")
         return view, below
+
+    # ---- mesh reconstruction ----------------------------------------------------------
+    def marching_cubes(self, volume, level=0.0, index_to_world=None):
+        """(verts [V,3] f32, faces [F,3] i32, normals [V,3] f32) on the device: isdf_marching_cubes of a [D0,D1,D2] volume, the
+        isosurface step of Trainer.mesh_rec (draw3D.py:111-160).  One launch at the cached capacity, one sync to read the counts,
+        one re-launch only on overflow; workspace and capacity are kept across calls (isdf_amd.mesh.Mesher)."""
+        if self._mesher is None:
+            from .mesh import Mesher
+            self._mesher = Mesher(self.device)
+        return self._mesher(volume, level, index_to_world)
 
     # ---- AdamW ----------------------------------------------------------------------
     def adamw(self, lr=0.0013, weight_decay=0.012, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0,

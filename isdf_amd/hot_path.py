@@ -8,6 +8,9 @@ reference `isdf.modules.trainer.Trainer` INSTANCE to the HIP kernels behind the 
     Trainer.is_keyframe         trainer.py:586-620   (fused sampler -> frozen net -> depth render)
     Trainer.get_data            trainer.py:530-562   (the reference's own method runs; its two geometry calls -- depth -> point cloud ->
                                                       8-neighbour normals, transform.py:169-196,215-270 -- are ONE stencil launch)
+    Trainer.get_sdf_grid        trainer.py:1426-1443 (one isdf_sdf_eval over grid_pc instead of 100k-point chunks)
+    Trainer.mesh_rec            trainer.py:1500-1542 (marching cubes in HIP, world affine in-kernel, one copy to the host;
+                                                      write_mesh / eval_mesh follow through it)
 
 ONE object owns the state: every attribute the reference's drivers and its own remaining methods read or
 write -- `tot_step_time`, `steps_since_frame`, `optim_frames`, `last_is_keyframe`, `noise_std`, `frames`,
@@ -541,6 +544,64 @@ class HotPath:
         finally:
             geo.pointcloud_from_depth_torch, geo.estimate_pointcloud_normals = saved
 
+    # ------------------------------------------------------------------ mesh reconstruction (trainer.py:1426-1443,1500-1542)
+    def get_sdf_grid(self):
+        """The network on the cached `grid_pc` as a [grid_dim]^3 volume: ONE forward launch over all grid_dim^3 points (the
+        reference's fc_map.chunks makes one per 100 000; the kernel's result per point does not depend on the chunking)."""
+        d = self.grid_dim
+        with torch.no_grad():
+            return self.engine.sdf_eval(self.grid_pc).view(d, d, d)
+
+    def _vis_pointcloud(self):
+        """world-frame point cloud of the keyframes at visualisation resolution (update_vis_vars + backproject + draw_pc)"""
+        ref = self._hip.ref_module
+        self.update_vis_vars()
+        pcs_cam = ref.geometry.transform.backproject_pointclouds(self.gt_depth_vis, self.fx_vis, self.fy_vis, self.cx_vis,
+                                                                 self.cy_vis)
+        pc, _ = ref.draw3D.draw_pc(len(self.frames), pcs_cam, self.frames.T_WC_batch_np)
+        return pc
+
+    def mesh_rec(self, crop_mesh_with_pc=True):
+        """The reconstructed mesh as a trimesh.Trimesh in world coordinates, what the reference's mesh_rec returns.
+
+        Contract kept: a trainer without a GT scene that runs incrementally first re-derives its scene bounds from the keyframes'
+        point cloud (set_scene_properties); with crop_mesh_with_pc, faces none of whose vertices lie within crop_dist of that
+        point cloud are dropped (a KDTree query on the host) together with the vertices left unreferenced; a pending grid size
+        (new_grid_dim / new_grid_pc) is swapped in at the end.  The point cloud is only built when one of the two needs it.
+
+        The mesh itself: get_sdf_grid, then Engine.marching_cubes with draw_mesh's index -> world chain as the kernel's affine
+        (isdf_amd.mesh.grid_index_to_world), so vertices and normals come out in world coordinates; ONE device -> host copy;
+        flat grey face colours as draw_mesh(..., color_by="none") sets them."""
+        from .mesh import grid_index_to_world
+        ref = self._hip.ref_module
+        if ref is None or not hasattr(ref, "trimesh"):
+            raise _ffi.IsdfError("mesh_rec needs the reference's trainer module (trimesh, KDTree, draw3D)")
+        rescale = self.gt_scene is False and self.incremental
+        pc = self._vis_pointcloud() if (crop_mesh_with_pc or rescale) else None
+        if rescale:
+            self.set_scene_properties(ref.trimesh.PointCloud(pc))
+        sdf = self.get_sdf_grid()
+        A = grid_index_to_world(self.grid_dim, self.scene_scale_np, self.bounds_transform_np)
+        verts, faces, normals = self.engine.marching_cubes(sdf, 0.0, A)
+        nv, nf = verts.shape[0], faces.shape[0]
+        flat = torch.cat([verts.reshape(-1), normals.reshape(-1), faces.reshape(-1).view(torch.float32)]).cpu().numpy()
+        verts_h = flat[:3 * nv].reshape(nv, 3)
+        normals_h = flat[3 * nv:6 * nv].reshape(nv, 3)
+        faces_h = flat[6 * nv:].view(np.int32).reshape(nf, 3)
+        if crop_mesh_with_pc:
+            near = ref.KDTree(pc).query(verts_h, k=1)[0] < self.crop_dist
+            faces_h = faces_h[near[faces_h].any(axis=1)]
+            used = np.zeros(nv, bool)
+            used[faces_h.reshape(-1)] = True
+            remap = np.cumsum(used) - 1
+            verts_h, normals_h, faces_h = verts_h[used], normals_h[used], remap[faces_h].astype(np.int32)
+        mesh = ref.trimesh.Trimesh(vertices=verts_h, vertex_normals=normals_h, faces=faces_h)
+        mesh.visual.face_colors = [160, 160, 160, 255]
+        if self.new_grid_dim is not None:
+            self.grid_dim, self.grid_pc = self.new_grid_dim, self.new_grid_pc
+            self.new_grid_dim = self.new_grid_pc = None
+        return mesh
+
     # ------------------------------------------------------------------ data parallel (SURVEY 8e, C2)
     def check_keyframe_latest(self):
         """The reference's decision logic (trainer.py:622-650) runs unchanged; under data parallelism rank 0's
@@ -754,6 +815,8 @@ def graft(trainer, rng="philox", seed=1, dist_group=None, fix_normal_window=Fals
     hip.geometry_transform = geo if (geo is not None and hasattr(geo, "pointcloud_from_depth_torch")
                                      and hasattr(geo, "estimate_pointcloud_normals")) else None
     hip.ingest_launches = 0
+    # the module whose trimesh / KDTree / draw3D / geometry the bound mesh_rec uses: the trainer class's own module
+    hip.ref_module = sys.modules.get(trainer.__class__.__module__)
     if migrate_frames and getattr(trainer, "frames", None) is not None and not isinstance(trainer.frames, frame_store.FrameData):
         trainer.frames = frame_store.FrameData.from_reference(trainer.frames)     # same fields, the existing keyframes carried over
     trainer._hip = hip

@@ -1,0 +1,114 @@
+"""Mesh reconstruction on the device: marching cubes of a dense SDF volume (`isdf_marching_cubes`, include/isdf_hip.h) and the
+index -> world affine of the reference's `draw3D.draw_mesh` (draw3D.py:128-160).
+
+    verts, faces, normals = marching_cubes(sdf_grid, level=0.0, index_to_world=grid_index_to_world(dim, scale, T))
+
+gives, on the device, the vertices and normals `draw_mesh(sdf_grid, scale, T)` ends up with, and int32 faces.  The mesh is
+indexed (one vertex per sign-changing grid edge) and bit-reproducible: vertices are ordered by the grid point owning their edge,
+then axis; faces by cell, then table order (tables: isdf_amd/mc_tables.py)."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _ffi
+
+
+def grid_index_to_world(dim, scene_scale, bounds_transform):
+    """[3, 4] float32 affine of draw_mesh's chain on a dim^3 grid: v / (dim - 1) -> - 0.5 -> x 2 -> x scene_scale (per axis) ->
+    bounds_transform (4 x 4).  `Trainer.grid_pc` holds exactly these points (make_3D_grid over [-1, 1], trainer.py:141-148)."""
+    s = np.broadcast_to(np.asarray(scene_scale, np.float64).reshape(-1), (3,))
+    T = np.asarray(bounds_transform, np.float64).reshape(4, 4)
+    R = T[:3, :3]
+    A = np.empty((3, 4), np.float64)
+    A[:, :3] = R * (2.0 * s / (dim - 1))[None, :]
+    A[:, 3] = T[:3, 3] - R @ s
+    return A.astype(np.float32)
+
+
+class Mesher:
+    """Caller-side state of `isdf_marching_cubes` on one device: the workspace, the device / pinned-host count pair and the
+    output capacity, all kept across calls.  Each call makes ONE launch sequence at the current capacity, synchronises once to
+    read the counts, and re-launches once with exact capacity only if the mesh did not fit (the capacity then stays grown).
+    The returned tensors are fresh (torch's caching allocator): a later call does not overwrite them."""
+
+    def __init__(self, device):
+        self.lib = _ffi.lib()
+        self.device = torch.device(device)
+        self._ws = None
+        self.counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self.counts_host = torch.zeros(2, dtype=torch.int64, pin_memory=True)
+        self.cap = None
+        self.launches = 0        # marching-cubes launch sequences so far (the overflow path makes two for one call)
+
+    @staticmethod
+    def estimate(D0, D1, D2):
+        """vertices / faces to allocate before the first call: a surface that crosses every slab of the grid a few times"""
+        v = 4 * (D0 * D1 + D1 * D2 + D0 * D2) + 4096
+        return v, 2 * v + 4096
+
+    def _launch(self, args, V, F, stream):
+        verts = torch.empty(V, 3, dtype=torch.float32, device=self.device)
+        normals = torch.empty(V, 3, dtype=torch.float32, device=self.device)
+        faces = torch.empty(F, 3, dtype=torch.int32, device=self.device)
+        _ffi.check(self.lib.isdf_marching_cubes(C.byref(args), _ffi.ptr(self.counts), _ffi.ptr(verts), _ffi.ptr(normals), V,
+                                                _ffi.ptr(faces), F, _ffi.ptr(self._ws), self._ws.numel(), stream),
+                   "isdf_marching_cubes")
+        self.launches += 1
+        self.counts_host.copy_(self.counts, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        nv, nf = (int(x) for x in self.counts_host.tolist())
+        return verts, faces, normals, nv, nf
+
+    def __call__(self, volume, level=0.0, index_to_world=None, capacity=None):
+        from .engine import _stream
+        if volume.dim() != 3:
+            raise ValueError("marching_cubes takes a [D0, D1, D2] volume (got shape %s)" % (tuple(volume.shape),))
+        vol = volume.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        D0, D1, D2 = (int(d) for d in vol.shape)
+        args = _ffi.McArgs()
+        args.volume, args.D0, args.D1, args.D2, args.level = vol.data_ptr(), D0, D1, D2, float(level)
+        if index_to_world is not None:
+            A = np.asarray(index_to_world.detach().cpu() if torch.is_tensor(index_to_world) else index_to_world,
+                           np.float32).reshape(3, 4)
+            args.has_transform = 1
+            args.index_to_world[:] = [float(x) for x in A.reshape(-1)]
+        nb = self.lib.isdf_mesh_ws_bytes(D0, D1, D2)
+        _ffi.check(min(nb, 0), "isdf_mesh_ws_bytes(%d, %d, %d)" % (D0, D1, D2))
+        if self._ws is None or self._ws.numel() < nb:
+            self._ws = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+        if capacity is not None:
+            V, F = capacity
+        else:
+            est = self.estimate(D0, D1, D2)
+            V, F = (est if self.cap is None else (max(self.cap[0], est[0]), max(self.cap[1], est[1])))
+        stream = _stream(self.device)
+        verts, faces, normals, nv, nf = self._launch(args, V, F, stream)
+        if nv > V or nf > F:            # did not fit: nothing was written; once more at the exact size
+            V, F = max(nv, 1), max(nf, 1)
+            verts, faces, normals, nv2, nf2 = self._launch(args, V, F, stream)
+            assert (nv2, nf2) == (nv, nf), ((nv, nf), (nv2, nf2))
+        if capacity is None:
+            grown = (max(V, nv + nv // 4), max(F, nf + nf // 4))
+            self.cap = grown if self.cap is None else (max(self.cap[0], grown[0]), max(self.cap[1], grown[1]))
+        return verts[:nv], faces[:nf], normals[:nv]
+
+
+_MESHERS = {}
+
+
+def marching_cubes(volume, level=0.0, index_to_world=None):
+    """Marching cubes of a device volume [D0, D1, D2] (vol[i][j][k], as `sdf.view(dim, dim, dim)` lays it out) at `level`.
+
+    Returns (verts [V, 3] f32, faces [F, 3] int32, normals [V, 3] f32), all on the volume's device.  A corner is inside iff
+    value < level; cells with a non-finite corner are skipped.  Normals are the interpolated central-difference gradient,
+    normalised: they point toward increasing value (free space for an SDF), and every face's right-hand normal agrees.
+    index_to_world: optional [3, 4] affine applied in the kernel (normals by its inverse transpose), e.g. `grid_index_to_world`."""
+    dev = volume.device
+    if dev.type != "cuda":
+        raise _ffi.IsdfError("isdf_amd marching cubes needs a HIP device (got %s); there is no CPU path" % dev)
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    m = _MESHERS.get(key)
+    if m is None:
+        m = _MESHERS[key] = Mesher(torch.device("cuda", key))
+    return m(volume, level, index_to_world)
