@@ -421,6 +421,67 @@ int isdf_marching_cubes(const isdf_mc_args* args, int64_t* counts, float* verts,
  * -1 padded.                                                                  */
 int isdf_mc_tables(int32_t* edge_corners_host, int8_t* tri_table_host);
 
+/* ---- rendered views -----------------------------------------------------
+ * The depth / normal renders of Trainer.render_depth_vis, render_normals_vis and
+ * latest_frame_vis (trainer.py:1225-1280,1055-1147) for B views at once: per ray
+ * of an H x W raster, S stratified samples (sample.stratified_sample +
+ * sample_along_rays, sample.py:77-178, no surface samples), the network
+ * (isdf_sdf_eval), the first crossing (render.sdf_render_depth, render.py:12-35,
+ * as isdf_render_depth without a depth sample) and, optionally, camera-frame
+ * normals at the rendered depth (render.render_normals, render.py:38-57:
+ * n_C = inverse(R_WC) (-g / (|g| + 1e-4)), the GENERAL 3x3 inverse, and a ray of
+ * depth 0 is evaluated at the camera origin).  Ray r = i * W + j of view b.
+ * The depth range of a ray has three sources (range_mode):
+ *   ISDF_RANGE_SCALAR   [min_depth, max_depth] for every ray: the coarse pass of
+ *                       latest_frame_vis (trainer.py:1091-1099); the bin limits
+ *                       are torch.linspace(min, max, S + 1) and bin_length is the
+ *                       caller's double (max - min) / S rounded to fp32;
+ *   ISDF_RANGE_DEPTH    [min_depth, resize(src_depth[b]) + depth_offset]:
+ *                       render_depth_vis (trainer.py:1237-1252; depth_offset 0.8),
+ *                       resize = OpenCV INTER_LINEAR from src_H x src_W to H x W
+ *                       (src = (dst + 0.5) * src_n / dst_n - 0.5, clamped at the
+ *                       borders, no antialiasing);
+ *   ISDF_RANGE_UPSAMPLE [d - depth_offset, d + depth_offset], d = the bilinear
+ *                       align_corners=True upsample of src_depth[b] (the previous
+ *                       pass's [src_H, src_W] depth) to H x W: the fine pass of
+ *                       latest_frame_vis (trainer.py:1105-1119; depth_offset 0.1).
+ * For the last two the limits are linspace(0, 1, S + 1) * (max - min) + min and
+ * bin_length = (max - min) / S in fp32 (sample.py:94-105); z = limit + u * bin_length. */
+enum { ISDF_RANGE_SCALAR = 0, ISDF_RANGE_DEPTH = 1, ISDF_RANGE_UPSAMPLE = 2 };
+
+typedef struct isdf_render_args {
+  int32_t n_views;           /* B >= 0 (0: the call is a no-op)                                    */
+  int32_t H, W;              /* view raster, R = H * W rays per view                               */
+  int32_t n_samples;         /* S >= 1 (unused when depth_in is given)                             */
+  const float* T_WC;         /* [B,4,4] camera-to-world poses (frames.T_WC_batch / T_WC_track)     */
+  const float* dirs_C;       /* [R,3] camera-frame ray directions (trainer.dirs_C_vis[_up])        */
+  int32_t range_mode;        /* ISDF_RANGE_*                                                        */
+  float min_depth;           /* SCALAR / DEPTH: trainer.min_depth                                   */
+  float max_depth;           /* SCALAR: trainer.max_depth                                           */
+  float bin_length;          /* SCALAR: (max_depth - min_depth) / S                                 */
+  float depth_offset;        /* DEPTH: 0.8 (trainer.py:1244); UPSAMPLE: 0.1 (trainer.py:1113-1114)   */
+  int32_t src_H, src_W;      /* DEPTH / UPSAMPLE: raster of src_depth                               */
+  int32_t rng_mode;          /* 0: draw_u [B,R,S] injected (torch.rand(R, S) per view, sample.py:123);
+                                1: in-kernel Philox4x32-10 keyed by seed, counter (render counter),
+                                view and ray; not stream-compatible with torch                       */
+  const float* src_depth;    /* DEPTH: [B,src_H,src_W] keyframe depth; UPSAMPLE: [B,src_H,src_W]   */
+  const float* draw_u;       /* rng_mode 0                                                          */
+  uint64_t seed, counter;    /* rng_mode 1                                                          */
+  const float* depth_in;     /* [B,R] or NULL: the depth is GIVEN (render_normals_vis) -- no samples,
+                                no render; normals_out is then required                              */
+} isdf_render_args;
+
+/* workspace bytes of isdf_render_views for n_views x (H * W) rays x n_samples (ISDF_EINVAL on bad sizes).
+ * After a call that renders, the workspace BEGINS with z_vals [B,R,S] f32 followed by pc [B,R,S,3] f32
+ * (the samples of that call, for parity checks).                                                         */
+int64_t isdf_render_ws_bytes(const isdf_net_cfg* net, int32_t n_views, int32_t H, int32_t W, int32_t n_samples);
+
+/* depth_out [B,R] (or NULL), normals_out [B,R,3] (or NULL); at least one of them.  Launches on `stream`:
+ * samples, forward, first crossing (unless depth_in), then points, forward with input gradient and the
+ * camera-frame rotation (if normals_out).  The workspace needs no initialisation.                        */
+int isdf_render_views(const isdf_net_cfg* net, const float* params, const void* shadow, const isdf_render_args* args,
+                      float* depth_out, float* normals_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ SYMBOLS = [
     "isdf_sample_rays",
     "isdf_sdf_eval", "isdf_train_step", "isdf_train_step_adamw", "isdf_train_step_finish", "isdf_bounds_pc",
     "isdf_frame_avg", "isdf_adamw", "isdf_estimate_normals", "isdf_render_depth", "isdf_allreduce_sum_f32",
-    "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables",
+    "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables", "isdf_render_ws_bytes", "isdf_render_views",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -93,6 +93,17 @@ class McArgs(C.Structure):
                 ("has_transform", C.c_int32), ("index_to_world", C.c_float * 12)]
 
 
+RANGE_SCALAR, RANGE_DEPTH, RANGE_UPSAMPLE = 0, 1, 2
+
+
+class RenderArgs(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_samples", C.c_int32),
+                ("T_WC", C.c_void_p), ("dirs_C", C.c_void_p), ("range_mode", C.c_int32), ("min_depth", C.c_float),
+                ("max_depth", C.c_float), ("bin_length", C.c_float), ("depth_offset", C.c_float), ("src_H", C.c_int32),
+                ("src_W", C.c_int32), ("rng_mode", C.c_int32), ("src_depth", C.c_void_p), ("draw_u", C.c_void_p),
+                ("seed", C.c_uint64), ("counter", C.c_uint64), ("depth_in", C.c_void_p)]
+
+
 
 class IsdfError(RuntimeError):
     pass
@@ -143,9 +154,12 @@ def lib():
     L.isdf_mesh_ws_bytes.argtypes = [i32, i32, i32]
     L.isdf_marching_cubes.argtypes = [P(McArgs), vp, vp, vp, i64, vp, i64, vp, i64, vp]
     L.isdf_mc_tables.argtypes = [vp, vp]
+    L.isdf_render_ws_bytes.argtypes = [P(NetCfg), i32, i32, i32, i32]
+    L.isdf_render_views.argtypes = [P(NetCfg), vp, vp, P(RenderArgs), vp, vp, vp, i64, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64
+    L.isdf_render_ws_bytes.restype = i64
     if L.isdf_abi_version() != ABI_VERSION:
         raise IsdfError("libisdf_hip.so ABI %d != binding ABI %d" % (L.isdf_abi_version(), ABI_VERSION))
     _lib = L

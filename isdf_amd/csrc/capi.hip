@@ -42,6 +42,10 @@ int launch_marching_cubes(const float* vol, int32_t D0, int32_t D1, int32_t D2, 
                           int64_t* counts, float* verts, float* normals, int64_t max_verts, int32_t* faces, int64_t max_faces,
                           void* workspace, hipStream_t st);
 void mc_tables_host(int32_t* edge_corners, int8_t* tri_table);
+int launch_render_samples(const isdf_render_args& a, float* z, float* pc, hipStream_t st);
+int launch_normal_points(const float* T_WC, const float* dirs_C, int64_t R, int64_t n_rays, const float* depth, float* pts,
+                         hipStream_t st);
+int launch_normal_finish(const float* T_WC, int64_t R, int64_t n_rays, const float* grad, float* normals, hipStream_t st);
 }  // namespace isdf
 
 namespace isdf { thread_local int g_isdf_last_hip_error = 0; }
@@ -386,6 +390,84 @@ int isdf_marching_cubes(const isdf_mc_args* a, int64_t* counts, float* verts, fl
 int isdf_mc_tables(int32_t* edge_corners_host, int8_t* tri_table_host) {
   mc_tables_host(edge_corners_host, tri_table_host);
   return ISDF_OK;
+}
+
+// ---- rendered views: workspace = z [B*R*S] | pc [B*R*S*3] | sdf [B*R*S] | depth [B*R] | normal points [B*R*3] |
+// their sdf [B*R] | gradient [B*R*3] | the input-gradient forward's own workspace for B*R points; 256-byte aligned pieces
+struct RenderWs { int64_t z, pc, sdf, depth, npts, nsdf, ngrad, fwd, fwdBytes, total; };
+
+static int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
+static int render_ws_layout(const isdf_net_cfg* net, int32_t B, int32_t H, int32_t W, int32_t S, RenderWs* w) {
+  if (B < 0 || H < 1 || W < 1 || S < 1) return ISDF_EINVAL;
+  NetLayout l; int rc = make_layout(net, &l);
+  if (rc) return rc;
+  if (!layout_supported(l)) return ISDF_EUNSUPPORTED;
+  const int64_t rays = (int64_t)B * H * W, pts = rays * S;
+  if ((int64_t)H * W > 0x7fffffff || pts > ((int64_t)1 << 40)) return ISDF_EINVAL;
+  WorkspaceLayout fw; make_workspace(l, rays > 0 ? rays : 1, 0, false, &fw);
+  int64_t o = 0;
+  w->z = o; o = align256(o + 4 * pts);
+  w->pc = o; o = align256(o + 12 * pts);
+  w->sdf = o; o = align256(o + 4 * pts);
+  w->depth = o; o = align256(o + 4 * rays);
+  w->npts = o; o = align256(o + 12 * rays);
+  w->nsdf = o; o = align256(o + 4 * rays);
+  w->ngrad = o; o = align256(o + 12 * rays);
+  w->fwd = o; w->fwdBytes = fw.totalBytes; o = align256(o + fw.totalBytes);
+  w->total = o;
+  return ISDF_OK;
+}
+
+int64_t isdf_render_ws_bytes(const isdf_net_cfg* net, int32_t n_views, int32_t H, int32_t W, int32_t n_samples) {
+  if (!net) return ISDF_EINVAL;
+  RenderWs w; int rc = render_ws_layout(net, n_views, H, W, n_samples, &w);
+  return rc ? rc : w.total;
+}
+
+int isdf_render_views(const isdf_net_cfg* net, const float* params, const void* shadow, const isdf_render_args* a,
+                      float* depth_out, float* normals_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!net || !a || !params || !shadow || (!depth_out && !normals_out)) return ISDF_EINVAL;
+  const bool given = a->depth_in != nullptr;
+  const int S = given ? 1 : a->n_samples;
+  RenderWs w; int rc = render_ws_layout(net, a->n_views, a->H, a->W, S, &w);
+  if (rc) return rc;
+  if (a->n_views == 0) return ISDF_OK;
+  if (!a->T_WC || !a->dirs_C || (given && !normals_out)) return ISDF_EINVAL;
+  if (!given) {
+    if (a->range_mode == ISDF_RANGE_SCALAR) {
+      if (!(a->bin_length >= 0.f)) return ISDF_EINVAL;
+    } else if (a->range_mode == ISDF_RANGE_DEPTH || a->range_mode == ISDF_RANGE_UPSAMPLE) {
+      if (!a->src_depth || a->src_H < 1 || a->src_W < 1) return ISDF_EINVAL;
+    } else {
+      return ISDF_EINVAL;
+    }
+    if ((a->rng_mode != 0 && a->rng_mode != 1) || (a->rng_mode == 0 && !a->draw_u)) return ISDF_EINVAL;
+  }
+  if (!workspace || workspace_bytes < w.total) return ISDF_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  const int64_t R = (int64_t)a->H * a->W, rays = (int64_t)a->n_views * R;
+  const float* depth = a->depth_in;
+  if (!given) {
+    float* z = (float*)(ws + w.z);
+    float* pc = (float*)(ws + w.pc);
+    float* sdf = (float*)(ws + w.sdf);
+    float* dst = depth_out ? depth_out : (float*)(ws + w.depth);
+    if ((rc = launch_render_samples(*a, z, pc, st))) return rc;
+    if ((rc = isdf_sdf_eval(net, params, shadow, pc, rays * S, nullptr, sdf, nullptr, nullptr, 0, stream))) return rc;
+    if ((rc = launch_render_depth(nullptr, rays, rays, S, z, sdf, nullptr, 0.f, dst, nullptr, st))) return rc;
+    depth = dst;
+  }
+  if (!normals_out) return ISDF_OK;
+  float* npts = (float*)(ws + w.npts);
+  float* ngrad = (float*)(ws + w.ngrad);
+  if ((rc = launch_normal_points(a->T_WC, a->dirs_C, R, rays, depth, npts, st))) return rc;
+  if ((rc = isdf_sdf_eval(net, params, shadow, npts, rays, nullptr, (float*)(ws + w.nsdf), ngrad, ws + w.fwd, w.fwdBytes,
+                          stream)))
+    return rc;
+  return launch_normal_finish(a->T_WC, R, rays, ngrad, normals_out, st);
 }
 
 }  // extern "C"

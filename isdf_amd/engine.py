@@ -200,6 +200,7 @@ class Engine:
         self._ws_key = None
         self._scan_ws = None      # sampler look-back state (zero on first use, self re-arming afterwards)
         self._mesher = None       # marching-cubes workspace, count pair and output capacity (isdf_amd.mesh.Mesher)
+        self._renderer = None     # rendered-view workspace (isdf_amd.render.Renderer)
         self.reduce_buf = None
         self.reduce_extra = 0
         self.reduce_floats = 0
@@ -623,6 +624,16 @@ class Engine:
             from .mesh import Mesher
             self._mesher = Mesher(self.device)
         return self._mesher(volume, level, index_to_world)
+
+    # ---- rendered views ----------------------------------------------------------
+    def render_views(self, T_WC, dirs_C, H, W, n_samples=0, **kw):
+        """(depth [B, H*W] or None, normals [B, H*W, 3] or None) on the device for the B poses of T_WC: isdf_render_views, the
+        renders of Trainer.render_depth_vis / render_normals_vis / latest_frame_vis (trainer.py:1055-1147,1225-1280) in one
+        pass; the options are isdf_amd.render.Renderer's.  The workspace is kept across calls."""
+        if self._renderer is None:
+            from .render import Renderer
+            self._renderer = Renderer(self)
+        return self._renderer(T_WC, dirs_C, H, W, n_samples, **kw)
 
     # ---- AdamW ----------------------------------------------------------------------
     def adamw(self, lr=0.0013, weight_decay=0.012, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0,

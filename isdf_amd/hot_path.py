@@ -11,6 +11,9 @@ reference `isdf.modules.trainer.Trainer` INSTANCE to the HIP kernels behind the 
     Trainer.get_sdf_grid        trainer.py:1426-1443 (one isdf_sdf_eval over grid_pc instead of 100k-point chunks)
     Trainer.mesh_rec            trainer.py:1500-1542 (marching cubes in HIP, world affine in-kernel, one copy to the host;
                                                       write_mesh / eval_mesh follow through it)
+    Trainer.render_depth_vis    trainer.py:1225-1262 (all keyframes in ONE isdf_render_views pass; the depth resize in-kernel)
+    Trainer.render_normals_vis  trainer.py:1264-1280 (all keyframes in one pass at the given depths; frames_vis follows)
+    Trainer.latest_frame_vis    trainer.py:1055-1147 (coarse pass, upsample, fine pass and normals on the device, one copy back)
 
 ONE object owns the state: every attribute the reference's drivers and its own remaining methods read or
 write -- `tot_step_time`, `steps_since_frame`, `optim_frames`, `last_is_keyframe`, `noise_std`, `frames`,
@@ -601,6 +604,90 @@ class HotPath:
             self.grid_dim, self.grid_pc = self.new_grid_dim, self.new_grid_pc
             self.new_grid_dim = self.new_grid_pc = None
         return mesh
+
+    # ------------------------------------------------------------------ rendered views (trainer.py:1055-1147,1225-1280)
+    def _render_rng(self, B, R, S):
+        """uniforms of one render pass: rng "torch" draws torch.rand(R, S) per view on the trainer's device, in the reference's
+        order (sample.py:123) -> dict(draws=[B, R, S]); "philox" advances the render counter (visualisation only: not part of
+        hip_state_dict) and leaves the torch generator alone"""
+        hip = self._hip
+        if hip.rng == "torch":
+            return dict(draws=torch.stack([torch.rand(R, S, device=self.device) for _ in range(B)]))
+        hip.render_count = getattr(hip, "render_count", 0) + 1
+        return dict(seed=hip.seed, counter=hip.render_count)
+
+    def _vis_poses(self):
+        T_WC_batch = self.frames.T_WC_batch
+        if self.frames.T_WC_track:                 # trainer.py:1229-1231 (a truthy track: a list of [4, 4] poses or a one-pose tensor)
+            T_WC_batch = self.frames.T_WC_track
+        if isinstance(T_WC_batch, (list, tuple)):
+            T_WC_batch = torch.stack([torch.as_tensor(t).reshape(4, 4) for t in T_WC_batch])
+        return T_WC_batch
+
+    def render_depth_vis(self):
+        """[K, H_vis, W_vis] depth of every keyframe from the map, on the device: ONE isdf_render_views pass over the K poses, the
+        depth range [min_depth, cv2.resize(depth, INTER_LINEAR) + 0.8] read from the device depth_batch (no host resize, no
+        upload), n_strat_samples stratified samples, first crossing.  No host synchronisation."""
+        K, H, W, S = len(self.frames), self.H_vis, self.W_vis, self.n_strat_samples
+        T = self._vis_poses()[:K]
+        rng = self._render_rng(K, H * W, S)
+        with torch.no_grad():
+            depth, _ = self.engine.render_views(T, self.dirs_C_vis[0], H, W, S, depth_images=self.frames.depth_batch[:K],
+                                                min_depth=self.min_depth, depth_offset=0.8, **rng)
+        return depth.view(K, H, W)
+
+    def render_normals_vis(self, view_depths):
+        """[K, H_vis, W_vis, 3] camera-frame normals at the given depths (render.render_normals per keyframe, render.py:38-57):
+        one pass of points, forward with input gradient and rotation by the inverse of each pose's 3x3 block."""
+        K, H, W = len(self.frames), self.H_vis, self.W_vis
+        T = self._vis_poses()[:K]
+        with torch.no_grad():
+            _, normals = self.engine.render_views(T, self.dirs_C_vis[0], H, W, depth=view_depths.reshape(K, H * W))
+        return normals.view(K, H, W, 3)
+
+    def latest_frame_vis(self, do_render=True):
+        """The reference's (rgbd_vis, render_vis, T_WC_np) and timing line.  The renders run on the device: a coarse pass of 20
+        samples over [min_depth, max_depth] on dirs_C_vis, the align-corners upsample and a fine pass of 12 samples over
+        d +- 0.1 on dirs_C_vis_up (in-kernel), normals at the fine depth; depth and normal image come back in one copy.
+        The host image work (cv2.resize, imgviz.depth2rgb, hstack) is the reference module's own.  do_render=False is the
+        reference's path."""
+        if not do_render:
+            return super().latest_frame_vis(do_render=False)
+        ref = self._hip.ref_module
+        start, end = ref.start_timing()
+        if self.live:
+            data = self.scene_dataset[0]
+            image, depth, T_WC_np = data['image'], data['depth'], data['T']
+        else:
+            image = self.frames.im_batch_np[-1]
+            depth = self.frames.depth_batch_np[-1]
+            T_WC_np = self.frames.T_WC_batch_np[-1]
+        w, h = self.W_vis_up * 2, self.H_vis_up * 2
+        image = ref.cv2.resize(image, (w, h))
+        depth = ref.cv2.resize(depth, (w, h))
+        depth_viz = ref.imgviz.depth2rgb(depth, min_value=self.min_depth, max_value=self.max_depth)
+        rgbd_vis = np.hstack((image, depth_viz))
+
+        T_WC = torch.FloatTensor(T_WC_np).to(self.device)[None, ...]
+        Hc, Wc, Hu, Wu = self.H_vis, self.W_vis, self.H_vis_up, self.W_vis_up
+        rng_c = self._render_rng(1, Hc * Wc, 20)
+        rng_f = self._render_rng(1, Hu * Wu, 12)
+        eng = self.engine
+        with torch.no_grad():
+            coarse, _ = eng.render_views(T_WC, self.dirs_C_vis, Hc, Wc, 20, scalar_range=(self.min_depth, self.max_depth),
+                                         **rng_c)
+            fine, normals = eng.render_views(T_WC, self.dirs_C_vis_up, Hu, Wu, 12, upsample=coarse.view(1, Hc, Wc),
+                                             depth_offset=0.1, want_normals=True, **rng_f)
+            normals = torch.clip((-normals + 1.0) / 2.0, 0., 1.)
+            host = torch.cat([fine.reshape(-1), normals.reshape(-1)]).cpu().numpy()
+        render_depth = host[:Hu * Wu].reshape(Hu, Wu)
+        render_depth_viz = ref.imgviz.depth2rgb(render_depth, min_value=self.min_depth, max_value=self.max_depth)
+        normals_viz = (host[Hu * Wu:].reshape(Hu, Wu, 3) * 255).astype(np.uint8)
+        render_vis = np.hstack((normals_viz, render_depth_viz))
+        render_vis = ref.cv2.resize(render_vis, (int(render_vis.shape[1] * 2), int(render_vis.shape[0] * 2)))
+        elapsed = ref.end_timing(start, end)
+        print("Time for depth and normal render", elapsed)
+        return rgbd_vis, render_vis, T_WC_np
 
     # ------------------------------------------------------------------ data parallel (SURVEY 8e, C2)
     def check_keyframe_latest(self):
