@@ -40,7 +40,7 @@ class NetConfig:
     #   fwd_operand "bf16").  None = the default for the forward mode.
     bwd_operand: Optional[str] = None
     # storage of the spilled P / GB tensors (include/isdf_hip.h `spill_operand`): None = auto (e4m3 bytes when n_freqs <= 6 with fp16
-    # second-order sweeps, i.e. replicaCAD.json / scanNet.json; 16-bit otherwise), "16bit", or "e4m3" (forced)
+    # second-order sweeps, i.e. replicaCAD.json / scanNet.json; 16-bit otherwise), "16bit", "e4m3" (forced) or "e4m3_gb" (GB only)
     spill_operand: Optional[str] = None
 
     @property

@@ -838,7 +838,8 @@ def graft(trainer, rng="philox", seed=1, dist_group=None, fix_normal_window=Fals
     virtual_step_ms: if set, the virtual clock advances by this much per step instead of the measured step time
          (the frame schedule is a function of measured time, trainer.py:100-101,1011-1013; pin it to compare runs).
     bwd_operand: "fp16" | "bf16" | None (default for the forward mode): operand / spill type of the second-order sweeps and dW.
-    spill_operand: None (auto) | "16bit" | "e4m3": storage of the spilled P / GB tensors (engine.NetConfig.spill_operand).
+    spill_operand: None (auto) | "16bit" | "e4m3" | "e4m3_gb": storage of the spilled P / GB tensors (engine.NetConfig.spill_operand;
+         "e4m3_gb": GB in e4m3, P in 16 bits; the e4m3 formats need hidden <= 256 and fp16 second-order sweeps).
     overlap_allreduce: data parallel only -- the closing reduction in two launches and the all-reduce in two parts, the first
          one on a side stream beside the second launch (dp.allreduce_split_); two collectives per step instead of one.
     migrate_frames: replace `trainer.frames` (the reference's FrameData: one torch.cat of the whole keyframe set per frame,
