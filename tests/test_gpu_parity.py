@@ -1005,6 +1005,8 @@ def test_batch_without_a_valid_ray_neither_hangs_nor_poisons_the_weights():
     eng = Engine(NetConfig(), "cuda")
     eng.params.normal_(0, 0.05); eng.pack()
     before = eng.params.clone()
+    eng.exp_avg.normal_(0, 1e-3); eng.exp_avg_sq.uniform_(0, 1e-6)       # a state the update would visibly move
+    state = [t.clone() for t in (eng.exp_avg, eng.exp_avg_sq, eng.shadow)]
     sc, lc = SampleConfig(n_rays=50, **cam), LossConfig()
     for fused in (True, False):
         s = eng.sample(depth, T, normal, idx, idx, sc, seed=3, offset=1)
@@ -1016,6 +1018,8 @@ def test_batch_without_a_valid_ray_neither_hangs_nor_poisons_the_weights():
         ls = eng.loss_sums().cpu().numpy()
         assert ls[4] == 0 and np.all(ls[:4] == 0)
         assert torch.equal(eng.params, before) and bool(torch.isfinite(eng.exp_avg).all())
+        # ... and neither moment nor the packed operand copies move (every route, bins and averages: tests/test_step_tail_gpu.py)
+        assert all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(state, (eng.exp_avg, eng.exp_avg_sq, eng.shadow)))
 
 
 def test_sampler_ordered_compaction_at_a_million_rays():
