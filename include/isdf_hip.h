@@ -482,6 +482,51 @@ int64_t isdf_render_ws_bytes(const isdf_net_cfg* net, int32_t n_views, int32_t H
 int isdf_render_views(const isdf_net_cfg* net, const float* params, const void* shadow, const isdf_render_args* args,
                       float* depth_out, float* normals_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- evaluation against ground truth ---------------------------------------
+ * The arithmetic of Trainer.eval_sdf, eval_object_sdf and eval_traj_cost after the network (trainer.py:1831-1866,
+ * 1993-2003,2026-2050) in ONE pass over the points: the ground-truth SDF by trilinear interpolation of an axis-aligned
+ * volume -- what sdf_util.eval_sdf_interp(handle_oob='mask') gets from scipy's linear RegularGridInterpolator
+ * (sdf_util.py:151-216) --, the validity mask, and every sum the three methods divide.
+ *   grid coordinate u = (p - origin) / spacing per axis; in bounds iff 0 <= u <= n - 1 on every axis (faces INCLUSIVE);
+ *   valid = in bounds and (gt != 0 or not exclude_zero_gt)   (trainer.py:1835 excludes zeros, :1993-2003 does not).
+ * record: ISDF_METRICS_RECORD doubles on the device,
+ *   [0] valid points  [1] in-bounds points  [2] sum |sdf - gt|
+ *   [3..8]  per bin of metrics.binned_losses (limits -inf, 0, 0.1, 0.2, 0.5, 1, +inf, strict on both sides) sum |sdf - gt|
+ *   [9..14] per bin the number of points
+ *   [15 + 3e ..] for epsilon 1, 1.5, 2 (e = 0, 1, 2): sum |chomp(sdf) - chomp(gt)|, sum chomp(sdf), sum chomp(gt)
+ *                (metrics.chomp_cost, metrics.py:95-104), all over the valid points.
+ * The record is bit-identical from run to run on the same inputs (per-block partial sums combined in block order).
+ * gt_out [n] (optional): the interpolated value, oob_fill where the point is out of bounds; valid_out [n] u8 (optional).
+ * workspace: ISDF_SDF_METRICS_WS_BYTES, no initialisation needed.  n = 0 writes a record of zeros.               */
+typedef struct isdf_gt_volume {
+  const float* values;        /* [nx][ny][nz] row-major fp32 on the device                  */
+  int32_t nx, ny, nz;         /* each >= 2, nx * ny * nz <= 2^31 - 1                         */
+  int32_t reserved;
+  float spacing[3];           /* > 0: transform[i][i] of the grid (sdf_util.py:151-159)      */
+  float origin[3];            /* transform[i][3]: world position of grid point (0, 0, 0)     */
+} isdf_gt_volume;
+
+#define ISDF_METRICS_RECORD 24
+#define ISDF_METRICS_MAX_BLOCKS 1024
+#define ISDF_SDF_METRICS_WS_BYTES (ISDF_METRICS_MAX_BLOCKS * ISDF_METRICS_RECORD * 8)
+
+int isdf_sdf_metrics(const isdf_gt_volume* vol, const float* pts, const float* sdf, int64_t n, int32_t exclude_zero_gt,
+                     float oob_fill, double* record, float* gt_out, uint8_t* valid_out, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
+/* Exact nearest-neighbour distances, the KD-tree queries of metrics.accuracy / completion (metrics.py:48-59), by brute
+ * force: dist[q] = min over t of |query[q] - target[t]| for query [n,3] and target [m,3] (m >= 1), fp32 on the device.
+ * The squared distance is (dx*dx + dy*dy) + dz*dz of the coordinate DIFFERENCES, each operation rounded to fp32, and
+ * dist its correctly rounded square root.  index (optional, int32 [n]): the nearest target, the lowest index on ties.
+ * dist_sum: one double on the device, the sum of dist in a fixed order (bit-identical run to run).  dist may be NULL.
+ * workspace: ISDF_NN_WS_BYTES(n), no initialisation needed; after the call it BEGINS with one 64-bit key per query,
+ * (bits of the squared distance) << 32 | index (index 0xffffffff when none was asked for), for parity checks.
+ * n = 0 writes dist_sum = 0.                                                                                      */
+#define ISDF_NN_WS_BYTES(n) (8 * (int64_t)(n) + 8 * (((int64_t)(n) + 255) / 256) + 256)
+
+int isdf_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
+                     double* dist_sum, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

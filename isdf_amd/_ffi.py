@@ -21,6 +21,7 @@ SYMBOLS = [
     "isdf_sdf_eval", "isdf_train_step", "isdf_train_step_adamw", "isdf_train_step_finish", "isdf_bounds_pc",
     "isdf_frame_avg", "isdf_adamw", "isdf_estimate_normals", "isdf_render_depth", "isdf_allreduce_sum_f32",
     "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables", "isdf_render_ws_bytes", "isdf_render_views",
+    "isdf_sdf_metrics", "isdf_nn_distance",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -103,6 +104,18 @@ class RenderArgs(C.Structure):
                 ("src_W", C.c_int32), ("rng_mode", C.c_int32), ("src_depth", C.c_void_p), ("draw_u", C.c_void_p),
                 ("seed", C.c_uint64), ("counter", C.c_uint64), ("depth_in", C.c_void_p)]
 
+class GtVolumeArgs(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("reserved", C.c_int32),
+                ("spacing", C.c_float * 3), ("origin", C.c_float * 3)]
+
+
+METRICS_RECORD = 24                                   # ISDF_METRICS_RECORD (doubles)
+SDF_METRICS_WS_BYTES = 1024 * METRICS_RECORD * 8      # ISDF_SDF_METRICS_WS_BYTES
+
+
+def nn_ws_bytes(n):
+    """ISDF_NN_WS_BYTES(n)"""
+    return 8 * int(n) + 8 * ((int(n) + 255) // 256) + 256
 
 
 class IsdfError(RuntimeError):
@@ -156,6 +169,8 @@ def lib():
     L.isdf_mc_tables.argtypes = [vp, vp]
     L.isdf_render_ws_bytes.argtypes = [P(NetCfg), i32, i32, i32, i32]
     L.isdf_render_views.argtypes = [P(NetCfg), vp, vp, P(RenderArgs), vp, vp, vp, i64, vp]
+    L.isdf_sdf_metrics.argtypes = [P(GtVolumeArgs), vp, vp, i64, i32, f32, vp, vp, vp, vp, i64, vp]
+    L.isdf_nn_distance.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64

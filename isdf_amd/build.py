@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
-SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "capi.hip"]
+SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "capi.hip"]
 HEADERS = ["isdf_common.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
@@ -27,9 +27,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 # mesh.hip: the vertex pass's affine (three rows against one point) vectorises into the same refused form; render.hip's ray
 # transform and camera-frame rotation are the same shape; its arithmetic restates torch's op by op, so it is also built without
 # floating-point contraction (a fused multiply-add moves the resampled depth range by a few ulp).
+# eval.hip: the nearest-neighbour loop holds four queries against one target; vectorised, the shared target becomes the
+# broadcast operand of the same refused form; its squared distances must equal an fp32 model bit for bit, so no contraction
+# either (the trilinear blend asks for its fused multiply-adds by name).
 PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"],
             "dw.hip": ["-fno-slp-vectorize"], "mesh.hip": ["-fno-slp-vectorize"],
-            "render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
+            "render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "eval.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
 
 
 def _hipcc():

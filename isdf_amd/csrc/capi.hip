@@ -46,6 +46,10 @@ int launch_render_samples(const isdf_render_args& a, float* z, float* pc, hipStr
 int launch_normal_points(const float* T_WC, const float* dirs_C, int64_t R, int64_t n_rays, const float* depth, float* pts,
                          hipStream_t st);
 int launch_normal_finish(const float* T_WC, int64_t R, int64_t n_rays, const float* grad, float* normals, hipStream_t st);
+int launch_sdf_metrics(const isdf_gt_volume& vol, const float* pts, const float* sdf, int64_t n, int exclude_zero,
+                       float oob_fill, double* record, float* gt_out, uint8_t* valid_out, double* part, hipStream_t st);
+int launch_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
+                       double* dist_sum, unsigned long long* keys, double* part, hipStream_t st);
 }  // namespace isdf
 
 namespace isdf { thread_local int g_isdf_last_hip_error = 0; }
@@ -468,6 +472,30 @@ int isdf_render_views(const isdf_net_cfg* net, const float* params, const void* 
                           stream)))
     return rc;
   return launch_normal_finish(a->T_WC, R, rays, ngrad, normals_out, st);
+}
+
+// ---- evaluation against ground truth (eval.hip)
+int isdf_sdf_metrics(const isdf_gt_volume* vol, const float* pts, const float* sdf, int64_t n, int32_t exclude_zero_gt,
+                     float oob_fill, double* record, float* gt_out, uint8_t* valid_out, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!vol || !record || n < 0 || (n > 0 && (!pts || !sdf))) return ISDF_EINVAL;
+  if (vol->nx < 2 || vol->ny < 2 || vol->nz < 2 || (int64_t)vol->nx * vol->ny * vol->nz > 0x7fffffff) return ISDF_EINVAL;
+  for (int k = 0; k < 3; ++k)
+    if (!(vol->spacing[k] > 0.f) || !__builtin_isfinite(vol->spacing[k]) || !__builtin_isfinite(vol->origin[k])) return ISDF_EINVAL;
+  if (n > 0 && !vol->values) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < ISDF_SDF_METRICS_WS_BYTES) return ISDF_EWORKSPACE;
+  return launch_sdf_metrics(*vol, pts, sdf, n, exclude_zero_gt != 0, oob_fill, record, gt_out, valid_out, (double*)workspace,
+                            (hipStream_t)stream);
+}
+
+int isdf_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
+                     double* dist_sum, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!dist_sum || n < 0 || n > ((int64_t)1 << 40) || (n > 0 && (!query || !target || m < 1 || m > 0xfffffffe))) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < ISDF_NN_WS_BYTES(n)) return ISDF_EWORKSPACE;
+  unsigned long long* keys = (unsigned long long*)workspace;
+  return launch_nn_distance(query, n, target, m, dist, index, dist_sum, keys, (double*)(keys + n), (hipStream_t)stream);
 }
 
 }  // extern "C"

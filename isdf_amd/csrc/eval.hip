@@ -1,0 +1,254 @@
+// Evaluation of the map against ground truth (Trainer.eval_sdf / eval_object_sdf / eval_traj_cost / eval_mesh,
+// trainer.py:1819-2064):
+//   sdf_util.eval_sdf_interp(handle_oob='mask')   isdf/datasets/sdf_util.py:183-216  (scipy's linear RegularGridInterpolator
+//                                                 over an axis-aligned grid, sdf_util.py:151-180)
+//   metrics.binned_losses                         isdf/eval/metrics.py:133-158
+//   metrics.chomp_cost                            isdf/eval/metrics.py:95-104
+//   metrics.accuracy / completion                 isdf/eval/metrics.py:48-59        (nearest-neighbour distances, brute force)
+// Both reductions are deterministic: per-block partial sums in double, combined in block order by one closing block; the
+// nearest neighbour is a minimum over integer keys (squared distance bits, then index), which no order can change.
+#include "isdf_common.h"
+
+namespace isdf {
+
+constexpr int REC = ISDF_METRICS_RECORD;          // doubles per record
+constexpr int MAXB = ISDF_METRICS_MAX_BLOCKS;     // per-block partial records in the workspace
+
+// CHOMP collision cost (metrics.py:95-104): -s + e/2; where s > 0: (s - e)^2 / (2e); where s > e: 0 (the last assignment wins)
+__device__ __forceinline__ double chomp(double s, double e) {
+  double c = -s + 0.5 * e;
+  if (s > 0.0) c = (1.0 / (2.0 * e)) * (s - e) * (s - e);
+  if (s > e) c = 0.0;
+  return c;
+}
+
+// sum over the 256 threads of a block in a fixed order: lanes by shuffle, then the four waves in wave order
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// One thread per point (grid-stride): grid coordinate, in-bounds test with the faces inclusive, trilinear value, validity,
+// and this point's share of the 24 sums.  Block b writes its partial record to part[b].
+__global__ __launch_bounds__(256) void sdf_metrics_kernel(const isdf_gt_volume vol, const float* __restrict__ pts,
+                                                          const float* __restrict__ sdf, int64_t n, int exclude_zero,
+                                                          float oob_fill, float* __restrict__ gt_out,
+                                                          uint8_t* __restrict__ valid_out, double* __restrict__ part) {
+  __shared__ double sh[4][REC];
+  double acc[REC];
+#pragma unroll
+  for (int v = 0; v < REC; ++v) acc[v] = 0.0;
+  const int nx = vol.nx, ny = vol.ny, nz = vol.nz;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float ux = (pts[i * 3] - vol.origin[0]) / vol.spacing[0];
+    const float uy = (pts[i * 3 + 1] - vol.origin[1]) / vol.spacing[1];
+    const float uz = (pts[i * 3 + 2] - vol.origin[2]) / vol.spacing[2];
+    const bool inb = ux >= 0.f && ux <= (float)(nx - 1) && uy >= 0.f && uy <= (float)(ny - 1) && uz >= 0.f &&
+                     uz <= (float)(nz - 1);
+    float gt = oob_fill;
+    if (inb) {
+      // cell index clamped to [0, n - 2] (a point on the upper face interpolates inside the last cell with t = 1)
+      const int ix = min((int)ux, nx - 2), iy = min((int)uy, ny - 2), iz = min((int)uz, nz - 2);
+      const float tx = ux - (float)ix, ty = uy - (float)iy, tz = uz - (float)iz;
+      const float* c = vol.values + ((int64_t)ix * ny + iy) * nz + iz;
+      const int64_t sx = (int64_t)ny * nz, sy = nz;
+      const float c00 = fmaf(tz, c[1] - c[0], c[0]);
+      const float c01 = fmaf(tz, c[sy + 1] - c[sy], c[sy]);
+      const float c10 = fmaf(tz, c[sx + 1] - c[sx], c[sx]);
+      const float c11 = fmaf(tz, c[sx + sy + 1] - c[sx + sy], c[sx + sy]);
+      const float c0 = fmaf(ty, c01 - c00, c00), c1 = fmaf(ty, c11 - c10, c10);
+      gt = fmaf(tx, c1 - c0, c0);
+    }
+    const bool valid = inb && (gt != 0.f || !exclude_zero);
+    if (gt_out) gt_out[i] = gt;
+    if (valid_out) valid_out[i] = valid ? 1 : 0;
+    acc[1] += inb ? 1.0 : 0.0;
+    if (valid) {
+      const double s = (double)sdf[i], g = (double)gt;
+      const double d = fabs(s - g);
+      acc[0] += 1.0;
+      acc[2] += d;
+      // metrics.binned_losses: limits -inf, 0, 0.1, 0.2, 0.5, 1, +inf, strict on both sides (compared in fp32 against the fp32
+      // ground truth; the limits are the doubles rounded to fp32)
+      const float lim[7] = {-INFINITY, 0.f, 0.1f, 0.2f, 0.5f, 1.f, INFINITY};
+#pragma unroll
+      for (int b = 0; b < 6; ++b) {
+        const bool in = gt > lim[b] && gt < lim[b + 1];
+        acc[3 + b] += in ? d : 0.0;
+        acc[9 + b] += in ? 1.0 : 0.0;
+      }
+#pragma unroll
+      for (int e = 0; e < 3; ++e) {
+        const double eps = 1.0 + 0.5 * e;
+        const double cp = chomp(s, eps), cg = chomp(g, eps);
+        acc[15 + 3 * e] += fabs(cp - cg);
+        acc[16 + 3 * e] += cp;
+        acc[17 + 3 * e] += cg;
+      }
+    }
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int v = 0; v < REC; ++v) {
+    const double t = wave_sum(acc[v]);
+    if (lane == 0) sh[wave][v] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < REC)
+    part[(int64_t)blockIdx.x * REC + threadIdx.x] =
+        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
+// closing block: out[v] = sum over the nPart partial records, each thread a strided share in ascending order, then the block's
+// fixed-order sum (width values per record)
+__global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restrict__ part, int64_t nPart, int width,
+                                                           double* __restrict__ out) {
+  __shared__ double sh[4];
+  for (int v = 0; v < width; ++v) {
+    double t = 0.0;
+    for (int64_t b = threadIdx.x; b < nPart; b += 256) t += part[b * width + v];
+    t = wave_sum(t);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) out[v] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  }
+}
+
+// ---- nearest neighbour, brute force -----------------------------------------------------------------------------------
+// Block (x, y): NN_Q queries per thread (1024 per block) against target chunk y.  A tile of NN_TILE targets sits in LDS one
+// axis per array, four targets per float4: every lane reads the SAME address (a broadcast ds_read_b128, no bank conflict),
+// three reads bring four targets, and each feeds all NN_Q queries held in registers -- 8 VALU operations per pair plus half a
+// v_min3 without the index, a compare and two selects with it, against 3/16 of an LDS read.  The squared distance is
+// (dx*dx + dy*dy) + dz*dz with every operation rounded to fp32 (the file is built with -ffp-contract=off, build.py), so it
+// equals a numpy float32 model bit for bit.  A chunk's result goes into the query's 64-bit key (distance bits << 32 | index)
+// by an integer atomic minimum: squared distances are >= 0, their bit patterns order like the values, and the lowest index
+// wins a tie whatever order the chunks finish in.
+constexpr int NN_Q = 4;
+constexpr int NN_TILE = 1024;
+
+template <bool IDX>
+__global__ __launch_bounds__(256) void nn_kernel(const float* __restrict__ query, int64_t n, const float* __restrict__ target,
+                                                 int64_t m, int64_t chunk, unsigned long long* __restrict__ keys) {
+  __shared__ float4 tx[NN_TILE / 4], ty[NN_TILE / 4], tz[NN_TILE / 4];   // four targets per 16-byte read and axis
+  const int64_t q0 = (int64_t)blockIdx.x * (256 * NN_Q) + threadIdx.x;
+  float qx[NN_Q], qy[NN_Q], qz[NN_Q], best[NN_Q];
+  uint32_t bi[NN_Q];
+#pragma unroll
+  for (int j = 0; j < NN_Q; ++j) {
+    const int64_t q = q0 + j * 256;
+    const bool ok = q < n;
+    qx[j] = ok ? query[q * 3] : 0.f; qy[j] = ok ? query[q * 3 + 1] : 0.f; qz[j] = ok ? query[q * 3 + 2] : 0.f;
+    best[j] = INFINITY; bi[j] = 0xffffffffu;
+  }
+  const int64_t t0 = (int64_t)blockIdx.y * chunk;
+  const int64_t t1 = t0 + chunk < m ? t0 + chunk : m;
+  for (int64_t base = t0; base < t1; base += NN_TILE) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NN_TILE / 256; ++j) {
+      const int k = threadIdx.x + j * 256;
+      const int64_t t = base + k;
+      // slots past the chunk hold +inf: their squared distance is +inf (or NaN) and never below the running minimum
+      const bool ok = t < t1;
+      ((float*)tx)[k] = ok ? target[t * 3] : INFINITY;
+      ((float*)ty)[k] = ok ? target[t * 3 + 1] : INFINITY;
+      ((float*)tz)[k] = ok ? target[t * 3 + 2] : INFINITY;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int k4 = 0; k4 < NN_TILE / 4; ++k4) {
+      const float4 X = tx[k4], Y = ty[k4], Z = tz[k4];
+      const float px[4] = {X.x, X.y, X.z, X.w}, py[4] = {Y.x, Y.y, Y.z, Y.w}, pz[4] = {Z.x, Z.y, Z.z, Z.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int j = 0; j < NN_Q; ++j) {
+          const float dx = __fsub_rn(qx[j], px[c]), dy = __fsub_rn(qy[j], py[c]), dz = __fsub_rn(qz[j], pz[c]);
+          const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+          if (IDX) {   // ascending index, strict: the lowest index of a tie
+            if (d2 < best[j]) { best[j] = d2; bi[j] = (uint32_t)(base + k4 * 4 + c); }
+          } else {
+            best[j] = fminf(best[j], d2);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NN_Q; ++j) {
+    const int64_t q = q0 + j * 256;
+    if (q < n) atomicMin(&keys[q], ((unsigned long long)__float_as_uint(best[j]) << 32) | bi[j]);
+  }
+}
+
+// key -> distance (correctly rounded square root), index, and the block's partial sum of the distances
+__global__ __launch_bounds__(256) void nn_finish_kernel(const unsigned long long* __restrict__ keys, int64_t n,
+                                                        float* __restrict__ dist, int32_t* __restrict__ index,
+                                                        double* __restrict__ part) {
+  __shared__ double sh[4];
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double d = 0.0;
+  if (q < n) {
+    const unsigned long long k = keys[q];
+    const float r = __fsqrt_rn(__uint_as_float((uint32_t)(k >> 32)));
+    if (dist) dist[q] = r;
+    if (index) index[q] = (int32_t)(uint32_t)k;
+    d = (double)r;
+  }
+  d = wave_sum(d);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = d;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+int launch_sdf_metrics(const isdf_gt_volume& vol, const float* pts, const float* sdf, int64_t n, int exclude_zero,
+                       float oob_fill, double* record, float* gt_out, uint8_t* valid_out, double* part, hipStream_t st) {
+  // the grid is a function of n alone, so the partial sums -- and with them every bit of the record -- repeat run to run
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > MAXB) blocks = MAXB;
+  if (blocks > 0) {
+    hipLaunchKernelGGL(sdf_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, st, vol, pts, sdf, n, exclude_zero, oob_fill,
+                       gt_out, valid_out, part);
+    const int rc = isdf_launch_status();
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, part, blocks, REC, record);
+  return isdf_launch_status();
+}
+
+int launch_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
+                       double* dist_sum, unsigned long long* keys, double* part, hipStream_t st) {
+  const int64_t fin = (n + 255) / 256;
+  if (n > 0) {
+    const hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)n * 8, st);   // every key starts above any (distance, index)
+    if (e != hipSuccess) { g_isdf_last_hip_error = (int)e; return ISDF_EHIP; }
+    // grid from the CU count: about four blocks (of four waves) per CU, reached by splitting the target set into chunks
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus < 1)
+      cus = 256;
+    const int64_t qblocks = (n + 256 * NN_Q - 1) / (256 * NN_Q);
+    const int64_t tiles = (m + NN_TILE - 1) / NN_TILE;
+    int64_t splits = (4 * (int64_t)cus + qblocks - 1) / qblocks;
+    if (splits > tiles) splits = tiles;
+    if (splits > 65535) splits = 65535;
+    if (splits < 1) splits = 1;
+    const int64_t chunk = (tiles + splits - 1) / splits * NN_TILE;
+    splits = (m + chunk - 1) / chunk;
+    const dim3 grid((unsigned)qblocks, (unsigned)splits);
+    if (index)
+      hipLaunchKernelGGL(nn_kernel<true>, grid, dim3(256), 0, st, query, n, target, m, chunk, keys);
+    else
+      hipLaunchKernelGGL(nn_kernel<false>, grid, dim3(256), 0, st, query, n, target, m, chunk, keys);
+    int rc = isdf_launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(nn_finish_kernel, dim3((unsigned)fin), dim3(256), 0, st, keys, n, dist, index, part);
+    if ((rc = isdf_launch_status())) return rc;
+  }
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, part, fin, 1, dist_sum);
+  return isdf_launch_status();
+}
+
+}  // namespace isdf

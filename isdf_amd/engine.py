@@ -201,6 +201,8 @@ class Engine:
         self._scan_ws = None      # sampler look-back state (zero on first use, self re-arming afterwards)
         self._mesher = None       # marching-cubes workspace, count pair and output capacity (isdf_amd.mesh.Mesher)
         self._renderer = None     # rendered-view workspace (isdf_amd.render.Renderer)
+        self._eval_ws = None      # partial records of isdf_sdf_metrics
+        self._nn_ws = None        # keys and partial sums of isdf_nn_distance
         self.reduce_buf = None
         self.reduce_extra = 0
         self.reduce_floats = 0
@@ -634,6 +636,51 @@ class Engine:
             from .render import Renderer
             self._renderer = Renderer(self)
         return self._renderer(T_WC, dirs_C, H, W, n_samples, **kw)
+
+    # ---- evaluation against ground truth -----------------------------------------------
+    def sdf_metrics(self, volume, pts, sdf, exclude_zero_gt=True, per_point=False, oob_fill=0.0):
+        """(record f64[24], gt [n] or None, valid u8[n] or None) on the device: isdf_sdf_metrics, the ground-truth lookup and
+        every sum of Trainer.eval_sdf / eval_object_sdf / eval_traj_cost (trainer.py:1831-1866,1993-2003,2026-2050) in one
+        pass.  `volume`: isdf_amd.metrics.GtVolume; pts [n,3], sdf [n].  No host synchronisation; isdf_amd.metrics.sdf_metrics
+        copies the record once and names its fields."""
+        p = pts.detach().reshape(-1, 3).to(device=self.device, dtype=torch.float32).contiguous()
+        s = sdf.detach().reshape(-1).to(device=self.device, dtype=torch.float32).contiguous()
+        n = int(p.shape[0])
+        if s.numel() != n:
+            raise ValueError("sdf_metrics: %d points but %d sdf values" % (n, s.numel()))
+        vd = volume.values.device
+        if vd.type != self.device.type or (self.device.index is not None and vd.index != self.device.index):
+            raise ValueError("sdf_metrics: the ground-truth volume is on %s, the engine on %s" % (volume.values.device, self.device))
+        if self._eval_ws is None:
+            self._eval_ws = torch.empty(_ffi.SDF_METRICS_WS_BYTES, dtype=torch.uint8, device=self.device)
+        record = torch.empty(_ffi.METRICS_RECORD, dtype=torch.float64, device=self.device)
+        gt = torch.empty(n, dtype=torch.float32, device=self.device) if per_point else None
+        valid = torch.empty(n, dtype=torch.uint8, device=self.device) if per_point else None
+        _ffi.check(self.lib.isdf_sdf_metrics(C.byref(volume.to_c()), _ffi.ptr(p), _ffi.ptr(s), n, int(bool(exclude_zero_gt)),
+                                             float(oob_fill), _ffi.ptr(record), _ffi.ptr(gt), _ffi.ptr(valid),
+                                             _ffi.ptr(self._eval_ws), int(self._eval_ws.numel()), _stream(self.device)),
+                   "isdf_sdf_metrics")
+        return record, gt, valid
+
+    def nn_distance(self, query, target, want_index=False):
+        """(dist [n] f32, index [n] i32 or None, dist_sum f64[1]) on the device: isdf_nn_distance, the exact distance from every
+        query point to its nearest target point (the KD-tree queries of metrics.accuracy / completion, metrics.py:48-59) by
+        brute force; the lowest target index on ties.  No host synchronisation."""
+        q = query.detach().reshape(-1, 3).to(device=self.device, dtype=torch.float32).contiguous()
+        t = target.detach().reshape(-1, 3).to(device=self.device, dtype=torch.float32).contiguous()
+        n, m = int(q.shape[0]), int(t.shape[0])
+        if n > 0 and m < 1:
+            raise ValueError("nn_distance: empty target set")
+        need = _ffi.nn_ws_bytes(n)
+        if self._nn_ws is None or self._nn_ws.numel() < need:
+            self._nn_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        dist = torch.empty(n, dtype=torch.float32, device=self.device)
+        index = torch.empty(n, dtype=torch.int32, device=self.device) if want_index else None
+        total = torch.empty(1, dtype=torch.float64, device=self.device)
+        _ffi.check(self.lib.isdf_nn_distance(_ffi.ptr(q), n, _ffi.ptr(t), m, _ffi.ptr(dist), _ffi.ptr(index), _ffi.ptr(total),
+                                             _ffi.ptr(self._nn_ws), int(self._nn_ws.numel()), _stream(self.device)),
+                   "isdf_nn_distance")
+        return dist, index, total
 
     # ---- AdamW ----------------------------------------------------------------------
     def adamw(self, lr=0.0013, weight_decay=0.012, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0,

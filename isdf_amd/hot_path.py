@@ -14,6 +14,12 @@ reference `isdf.modules.trainer.Trainer` INSTANCE to the HIP kernels behind the 
     Trainer.render_depth_vis    trainer.py:1225-1262 (all keyframes in ONE isdf_render_views pass; the depth resize in-kernel)
     Trainer.render_normals_vis  trainer.py:1264-1280 (all keyframes in one pass at the given depths; frames_vis follows)
     Trainer.latest_frame_vis    trainer.py:1055-1147 (coarse pass, upsample, fine pass and normals on the device, one copy back)
+    Trainer.eval_sdf            trainer.py:1819-1866 (ground-truth lookup, mask, L1, bins and CHOMP differences: ONE isdf_sdf_metrics
+                                                      pass over the device copy of gt_sdf_interp's grid, one copy of 24 doubles)
+    Trainer.eval_sdf_visible    trainer.py:1868-1905 (the cached sequence stays resident on the device; only new frames are uploaded)
+    Trainer.eval_object_sdf     trainer.py:1955-2008 (resident frames; per visible object one isdf_sdf_metrics call)
+    Trainer.eval_traj_cost      trainer.py:2010-2052 (validity count and both CHOMP sums from one record)
+    Trainer.eval_mesh           trainer.py:2054-2064 (accuracy / completion by isdf_nn_distance instead of two host KD-trees)
 
 ONE object owns the state: every attribute the reference's drivers and its own remaining methods read or
 write -- `tot_step_time`, `steps_since_frame`, `optim_frames`, `last_is_keyframe`, `noise_std`, `frames`,
@@ -24,8 +30,8 @@ reference's state_dict keys whose parameters are views of one flat buffer), `tra
 with the `torch.optim.AdamW` surface, `trainer.frames` an `isdf_amd.frame_store.FrameData` (the reference's fields and
 `add_frame_data` contract on geometrically growing buffers instead of one `torch.cat` of the whole keyframe set per frame,
 data_util.py:84-102; the existing keyframes migrate).  Everything else (`add_frame`, `add_data`,
-`check_keyframe_latest`, `select_keyframes`, evaluation, visualisation) keeps running as the
-reference's own code on the same object.
+`check_keyframe_latest`, `select_keyframes`, `eval_fixed`, `eval_sdf_volume`, the slices, the remaining visualisation)
+keeps running as the reference's own code on the same object.
 
 Where the reference is not importable (the GPU box, bench.py), `bench_support/standin_trainer.py` (test / bench infrastructure, outside
 this package) restates the driver-side methods; its `HipTrainer` is `graft()` applied to that stand-in -- the same code path.
@@ -688,6 +694,174 @@ class HotPath:
         elapsed = ref.end_timing(start, end)
         print("Time for depth and normal render", elapsed)
         return rgbd_vis, render_vis, T_WC_np
+
+    # ------------------------------------------------------------------ evaluation against ground truth (trainer.py:1819-2064)
+    def _gt_volume(self):
+        """`self.gt_sdf_interp`'s grid on the device (isdf_amd.metrics.GtVolume), uploaded once and re-made only if the attribute is
+        replaced; the interpolator itself is never called"""
+        from .metrics import GtVolume
+        hip, itp = self._hip, self.gt_sdf_interp
+        if itp is None:
+            raise _ffi.IsdfError("evaluation needs trainer.gt_sdf_interp (a ground-truth SDF grid)")
+        c = getattr(hip, "gt_volume", None)
+        if c is None or c[0] is not itp:
+            c = hip.gt_volume = (itp, GtVolume.from_interpolator(itp, hip.device))
+        return c[1]
+
+    def _eval_frames(self):
+        """(depth_batch [F,H,W], T_WC_batch [F,4,4]) of the cached sequence up to the virtual clock, as eval_sdf_visible and
+        eval_object_sdf build them (trainer.py:1869-1875,1968-1974) -- but RESIDENT: the reference converts and uploads the whole
+        sequence on every call (2 GB at 600 frames of 680 x 1200); here only the frames not yet on the device are read from
+        `self.cached_dataset` and copied.  Incremental runs ask for arange(int(tot_step_time * fps)), which only grows; the
+        non-incremental get_all() is uploaded once.  The cache lives on self._hip (not in hip_state_dict); drop_eval_cache()
+        releases it; a clock that went backwards or another dataset object starts it afresh."""
+        hip = self._hip
+        ds = self.cached_dataset
+        c = getattr(hip, "eval_cache", None)
+        mode = "incremental" if self.incremental else "all"
+        want = int(self.tot_step_time * self.fps) if self.incremental else 0
+        if c is None or c.dataset is not ds or c.mode != mode or want < c.asked:
+            c = hip.eval_cache = types.SimpleNamespace(dataset=ds, mode=mode, asked=0, held=0, depth=None, T=None,
+                                                       uploaded_frames=0, uploaded_bytes=0)
+        if mode == "all":
+            if c.depth is None:
+                sample = ds.get_all()
+                self._eval_cache_append(c, sample["depth"], sample["T"])
+        elif want > c.asked:
+            sample = ds[np.arange(c.asked, want)]
+            self._eval_cache_append(c, sample["depth"], sample["T"])
+            c.asked = want
+        if c.depth is None:                      # no frame yet: the reference's empty batch (its rays_per_frame then divides by 0)
+            return (torch.zeros(0, self.H, self.W, device=hip.device), torch.zeros(0, 4, 4, device=hip.device))
+        return c.depth[:c.held], c.T[:c.held]
+
+    def _eval_cache_append(self, c, depth, T):
+        """new frames -> the resident buffers (capacity grows by half, never beyond the dataset's length when it has one)"""
+        dev = self._hip.device
+        depth = torch.as_tensor(np.asarray(depth, np.float32))
+        T = torch.as_tensor(np.asarray(T, np.float32)).reshape(-1, 4, 4)
+        k = int(depth.shape[0])
+        if k == 0:
+            return
+        need = c.held + k
+        if c.depth is None or need > c.depth.shape[0]:
+            cap = need if c.mode == "all" else max(need, (c.held * 3) // 2, 32)
+            try:
+                cap = max(need, min(cap, len(c.dataset)))
+            except TypeError:
+                pass
+            nd = torch.empty((cap,) + tuple(depth.shape[1:]), dtype=torch.float32, device=dev)
+            nT = torch.empty(cap, 4, 4, dtype=torch.float32, device=dev)
+            if c.held:
+                nd[:c.held].copy_(c.depth[:c.held]); nT[:c.held].copy_(c.T[:c.held])
+            c.depth, c.T = nd, nT
+        c.depth[c.held:need].copy_(depth)
+        c.T[c.held:need].copy_(T)
+        c.held = need
+        c.uploaded_frames += k
+        c.uploaded_bytes += depth.numel() * 4 + T.numel() * 4
+
+    def drop_eval_cache(self):
+        """release the resident evaluation frames and the ground-truth volume (the next evaluation uploads them again)"""
+        self._hip.eval_cache = None
+        self._hip.gt_volume = None
+
+    def eval_sdf(self, samples=200000, visible_region=True):
+        """The reference's dict (av_l1, binned_l1 [6], l1_chomp_costs [3]; trainer.py:1819-1866).  The points come from
+        eval_sdf_visible (bound below) or the reference's own eval_sdf_volume; ground-truth interpolation, mask, L1, the six bins
+        and the CHOMP differences are ONE isdf_sdf_metrics pass and one copy of 24 doubles -- no point leaves the device."""
+        from . import metrics
+        if visible_region:
+            sdf, eval_pts = self.eval_sdf_visible(samples)
+        else:
+            sdf, eval_pts = self.eval_sdf_volume(samples)
+        return metrics.sdf_metrics(self.engine, self._gt_volume(), eval_pts, sdf, exclude_zero_gt=True).as_dict()
+
+    def eval_sdf_visible(self, samples=20000):
+        """(sdf [n], eval_pts [n,3]) of one sample per ray over the cached sequence (trainer.py:1868-1905): the same
+        sample_points call and the same noise_std=0 forward, so the generators advance as in the reference; the frames come
+        from the resident cache (_eval_frames).  The reference's ScanNet line (`dist_behind_surf == 0`, a comparison) has no effect."""
+        depth_batch, T_WC_batch = self._eval_frames()
+        rays_per_frame = samples // depth_batch.shape[0]
+        sample_pts = self.sample_points(depth_batch, T_WC_batch, n_rays=rays_per_frame, dist_behind_surf=self.dist_behind_surf,
+                                        n_strat_samples=1, n_surf_samples=0)
+        pc = sample_pts["pc"]
+        with torch.set_grad_enabled(False):
+            sdf = self.sdf_map(pc, noise_std=0)
+        return sdf.flatten(), pc.squeeze()
+
+    def eval_object_sdf(self, samples=10000):
+        """Per object the mean |sdf - gt| in a box around it, NaN while it is not visible (trainer.py:1955-2008).  The visibility
+        test is the reference's (100 random offsets per object, frustum.is_visible_torch) on the resident frames; per visible
+        object one isdf_sdf_metrics call that keeps zero-valued ground truth; the records come back in one copy."""
+        errors = None
+        if self.obj_bounds_file is not None:
+            ref = self._hip.ref_module
+            obj_bounds = ref.metrics.get_obj_eval_bounds(self.obj_bounds_file, self.up_ix)
+            obj_bounds = torch.FloatTensor(obj_bounds).to(self.device)
+            offsets = torch.rand(100, 3).to(self.device)
+            extents = obj_bounds[:, 1] - obj_bounds[:, 0]
+            pts = obj_bounds[:, 0] + offsets[:, None] * extents
+            depth_batch, T_WC_batch = self._eval_frames()
+            visible = ref.geometry.frustum.is_visible_torch(pts.view(-1, 3), T_WC_batch, depth_batch, self.H, self.W, self.fx,
+                                                            self.fy, self.cx, self.cy, trunc=0.05)
+            visible = visible.detach().cpu().numpy().sum(axis=0) > 0
+            visible = visible.reshape(100, len(obj_bounds))
+            visible = visible.sum(axis=0) / 100 > 0.5
+            vol, records = self._gt_volume(), []
+            for i in range(len(obj_bounds)):
+                if visible[i]:
+                    offsets = torch.rand(samples, 3).to(self.device)
+                    bounds = obj_bounds[i]
+                    pts = bounds[0] + offsets * (bounds[1] - bounds[0])[None, :]
+                    with torch.set_grad_enabled(False):
+                        sdf = torch.squeeze(self.sdf_map(pts))
+                    records.append(self.engine.sdf_metrics(vol, pts, sdf, exclude_zero_gt=False)[0])
+            host = torch.stack(records).cpu().numpy() if records else np.zeros((0, _ffi.METRICS_RECORD))
+            errors, k = [], 0
+            for i in range(len(obj_bounds)):
+                if visible[i]:
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        errors.append(np.float64(host[k, 2]) / np.float64(host[k, 0]))
+                    k += 1
+                else:
+                    errors.append(np.nan)
+        return errors
+
+    def eval_traj_cost(self, t_ahead=5.):
+        """(pred_chomp_costs [3], gt_chomp_costs [3]) summed along the next t_ahead seconds of the trajectory, or (nan, nan) when
+        fewer than 90 % of its points have a valid non-zero ground truth or the section is shorter than 30 poses
+        (trainer.py:2010-2052).  Network forward, then one isdf_sdf_metrics call: the validity count and both sets of sums
+        are fields of its record."""
+        from . import metrics
+        if self.traj_file:
+            traj = np.loadtxt(self.traj_file)
+            traj_start_ix = self.tot_step_time * 30
+            traj_end_ix = min(len(traj) - 1, (self.tot_step_time + t_ahead) * 30)
+            traj_section = traj[int(traj_start_ix): int(traj_end_ix)]
+            if len(traj_section) < 30:
+                return np.nan, np.nan
+            eval_pts = torch.from_numpy(np.ascontiguousarray(traj_section[:, [3, 7, 11]]))
+            with torch.set_grad_enabled(False):
+                sdf = self.sdf_map(eval_pts.float().to(self.device)).squeeze()
+            m = metrics.sdf_metrics(self.engine, self._gt_volume(), eval_pts, sdf, exclude_zero_gt=True)
+            if m.n_valid < 0.9 * len(traj_section):
+                return np.nan, np.nan
+            return m.pred_chomp_sums, m.gt_chomp_sums
+
+    def eval_mesh(self, samples=200000):
+        """(accuracy, completion) of the reconstructed mesh against the ground-truth scene mesh (trainer.py:2054-2064,
+        metrics.py:62-73): mesh_rec() and the two trimesh surface samplings are the reference's; the two nearest-neighbour
+        passes run on the device (isdf_nn_distance) instead of two host KD-trees."""
+        from . import metrics
+        ref = self._hip.ref_module
+        if ref is None or not hasattr(ref, "trimesh"):
+            raise _ffi.IsdfError("eval_mesh needs the reference's trainer module (trimesh)")
+        mesh_gt = ref.trimesh.load(self.scene_file)
+        sdf_mesh = self.mesh_rec()
+        rec_pc = ref.trimesh.sample.sample_surface(sdf_mesh, samples)
+        gt_pc = ref.trimesh.sample.sample_surface(mesh_gt, samples)
+        return metrics.accuracy_completion(self.engine, gt_pc[0], rec_pc[0])
 
     # ------------------------------------------------------------------ data parallel (SURVEY 8e, C2)
     def check_keyframe_latest(self):
