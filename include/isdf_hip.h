@@ -527,6 +527,45 @@ int isdf_sdf_metrics(const isdf_gt_volume* vol, const float* pts, const float* s
 int isdf_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
                      double* dist_sum, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- SDF slice images ---------------------------------------------------------
+ * What Trainer.compute_slices, obj_slices_vis and get_sdf_grid_pc do after the network (trainer.py:1593-1595,1603,
+ * 1617-1621,1629,1796-1807,1453-1461), in ONE pass over n points on the device:
+ *   colour      ScalarMappable.to_rgba(v, alpha=1., bytes=False), then (.. * 255).astype(np.uint8)[..., :3], through a
+ *               caller-supplied table: x = ((v - vmin) / range) * (float)n_colors, every operation rounded to fp32 (a true
+ *               division); NaN -> bad, x < 0 -> under, x == n_colors -> n_colors - 1, x > n_colors -> over, else (int)x.
+ *               Equal to matplotlib on every fp32 value when fp32 holds vmin and vmax - vmin exactly (the reference's tables:
+ *               -2, 2 and -0.5, 0.5); with other limits matplotlib subtracts and divides in double before it rounds, and a value
+ *               within a few fp32 roundings of a bin edge can land in the neighbouring bin.
+ *   ground truth sdf_util.eval_sdf_interp(gt_sdf_interp, pc, handle_oob='fill') (sdf_util.py:183-216): the trilinear value of
+ *               isdf_sdf_metrics (the same device function), oob_fill out of bounds.
+ *   CHOMP cost  metrics.chomp_cost(sdf, epsilon=chomp_eps) (metrics.py:95-104) of a float32 array, in numpy's order:
+ *               -s + eps/2; (1/(2 eps)) * ((s - eps) * (s - eps)) where s > 0; 0 where s > eps.
+ * Every output is optional (NULL): pred_rgb u8 [n,3] and pred_cost f32 [n] of sdf [n]; gt_out f32 [n], gt_rgb u8 [n,3] and
+ * gt_cost f32 [n] of the volume at pts [n,3].  cmap is needed by the colours, vol and pts by the ground-truth outputs, sdf by the
+ * predicted ones, chomp_eps > 0 by the costs; a call with no output, or an output without its input, is ISDF_EINVAL.
+ * n = 0 is a no-op.  No workspace, no atomics; the same inputs give the same bytes.                                          */
+typedef struct isdf_colormap {
+  const uint32_t* lut;  /* device [n_colors + 3], entry = R | G<<8 | B<<16;
+                           entries n_colors, n_colors+1, n_colors+2 = under, over, bad */
+  int32_t n_colors;     /* N >= 1 (<= ISDF_COLORMAP_MAX_COLORS: the table is staged in LDS) */
+  float vmin;           /* (float)norm.vmin */
+  float range;          /* (float)(norm.vmax - norm.vmin), > 0 */
+} isdf_colormap;
+
+#define ISDF_COLORMAP_MAX_COLORS 16381
+
+int isdf_slice_images(const float* pts, const float* sdf, int64_t n, const isdf_colormap* cmap, const isdf_gt_volume* vol,
+                      float oob_fill, float chomp_eps, uint8_t* pred_rgb, float* gt_out, uint8_t* gt_rgb, float* pred_cost,
+                      float* gt_cost, void* stream);
+
+/* The points of a plane raster, instead of an index_select on the trainer's grid_pc (trainer.py:1569-1576) or the
+ * linspace / meshgrid of obj_slices_vis (trainer.py:1785-1793): pts_out [H,W,3] fp32 on the device,
+ *   p[i][j] = (origin + (float)i * du) + (float)j * dv,   each operation rounded to fp32.
+ * origin, du, dv: three floats each in HOST memory (read before the call returns).  H * W = 0 is a no-op;
+ * H * W <= 2^31 - 1.                                                                                           */
+int isdf_plane_points(const float* origin, const float* du, const float* dv, int32_t H, int32_t W, float* pts_out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ SYMBOLS = [
     "isdf_sdf_eval", "isdf_train_step", "isdf_train_step_adamw", "isdf_train_step_finish", "isdf_bounds_pc",
     "isdf_frame_avg", "isdf_adamw", "isdf_estimate_normals", "isdf_render_depth", "isdf_allreduce_sum_f32",
     "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables", "isdf_render_ws_bytes", "isdf_render_views",
-    "isdf_sdf_metrics", "isdf_nn_distance",
+    "isdf_sdf_metrics", "isdf_nn_distance", "isdf_slice_images", "isdf_plane_points",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -109,6 +109,11 @@ class GtVolumeArgs(C.Structure):
                 ("spacing", C.c_float * 3), ("origin", C.c_float * 3)]
 
 
+class ColormapArgs(C.Structure):
+    _fields_ = [("lut", C.c_void_p), ("n_colors", C.c_int32), ("vmin", C.c_float), ("range", C.c_float)]
+
+
+COLORMAP_MAX_COLORS = 16381                           # ISDF_COLORMAP_MAX_COLORS
 METRICS_RECORD = 24                                   # ISDF_METRICS_RECORD (doubles)
 SDF_METRICS_WS_BYTES = 1024 * METRICS_RECORD * 8      # ISDF_SDF_METRICS_WS_BYTES
 
@@ -171,6 +176,8 @@ def lib():
     L.isdf_render_views.argtypes = [P(NetCfg), vp, vp, P(RenderArgs), vp, vp, vp, i64, vp]
     L.isdf_sdf_metrics.argtypes = [P(GtVolumeArgs), vp, vp, i64, i32, f32, vp, vp, vp, vp, i64, vp]
     L.isdf_nn_distance.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]
+    L.isdf_slice_images.argtypes = [vp, vp, i64, P(ColormapArgs), P(GtVolumeArgs), f32, f32, vp, vp, vp, vp, vp, vp]
+    L.isdf_plane_points.argtypes = [P(f32), P(f32), P(f32), i32, i32, vp, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64

@@ -50,6 +50,11 @@ int launch_sdf_metrics(const isdf_gt_volume& vol, const float* pts, const float*
                        float oob_fill, double* record, float* gt_out, uint8_t* valid_out, double* part, hipStream_t st);
 int launch_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
                        double* dist_sum, unsigned long long* keys, double* part, hipStream_t st);
+int launch_slice_images(const isdf_colormap* cmap, const isdf_gt_volume* vol, const float* pts, const float* sdf, int64_t n,
+                        float oob_fill, float chomp_eps, uint8_t* pred_rgb, float* gt_out, uint8_t* gt_rgb, float* pred_cost,
+                        float* gt_cost, hipStream_t st);
+int launch_plane_points(const float* origin, const float* du, const float* dv, int32_t H, int32_t W, float* pts_out,
+                        hipStream_t st);
 }  // namespace isdf
 
 namespace isdf { thread_local int g_isdf_last_hip_error = 0; }
@@ -475,14 +480,19 @@ int isdf_render_views(const isdf_net_cfg* net, const float* params, const void* 
 }
 
 // ---- evaluation against ground truth (eval.hip)
+static bool gt_volume_ok(const isdf_gt_volume* vol) {
+  if (vol->nx < 2 || vol->ny < 2 || vol->nz < 2 || (int64_t)vol->nx * vol->ny * vol->nz > 0x7fffffff) return false;
+  for (int k = 0; k < 3; ++k)
+    if (!(vol->spacing[k] > 0.f) || !__builtin_isfinite(vol->spacing[k]) || !__builtin_isfinite(vol->origin[k])) return false;
+  return true;
+}
+
 int isdf_sdf_metrics(const isdf_gt_volume* vol, const float* pts, const float* sdf, int64_t n, int32_t exclude_zero_gt,
                      float oob_fill, double* record, float* gt_out, uint8_t* valid_out, void* workspace,
                      int64_t workspace_bytes, void* stream) {
   isdf_clear_stale_hip_error();
   if (!vol || !record || n < 0 || (n > 0 && (!pts || !sdf))) return ISDF_EINVAL;
-  if (vol->nx < 2 || vol->ny < 2 || vol->nz < 2 || (int64_t)vol->nx * vol->ny * vol->nz > 0x7fffffff) return ISDF_EINVAL;
-  for (int k = 0; k < 3; ++k)
-    if (!(vol->spacing[k] > 0.f) || !__builtin_isfinite(vol->spacing[k]) || !__builtin_isfinite(vol->origin[k])) return ISDF_EINVAL;
+  if (!gt_volume_ok(vol)) return ISDF_EINVAL;
   if (n > 0 && !vol->values) return ISDF_EINVAL;
   if (!workspace || workspace_bytes < ISDF_SDF_METRICS_WS_BYTES) return ISDF_EWORKSPACE;
   return launch_sdf_metrics(*vol, pts, sdf, n, exclude_zero_gt != 0, oob_fill, record, gt_out, valid_out, (double*)workspace,
@@ -496,6 +506,36 @@ int isdf_nn_distance(const float* query, int64_t n, const float* target, int64_t
   if (!workspace || workspace_bytes < ISDF_NN_WS_BYTES(n)) return ISDF_EWORKSPACE;
   unsigned long long* keys = (unsigned long long*)workspace;
   return launch_nn_distance(query, n, target, m, dist, index, dist_sum, keys, (double*)(keys + n), (hipStream_t)stream);
+}
+
+// ---- SDF slice images (slices.hip)
+int isdf_slice_images(const float* pts, const float* sdf, int64_t n, const isdf_colormap* cmap, const isdf_gt_volume* vol,
+                      float oob_fill, float chomp_eps, uint8_t* pred_rgb, float* gt_out, uint8_t* gt_rgb, float* pred_cost,
+                      float* gt_cost, void* stream) {
+  isdf_clear_stale_hip_error();
+  const bool pred = pred_rgb || pred_cost, gt = gt_out || gt_rgb || gt_cost;
+  if (n < 0 || n > ((int64_t)1 << 40) || (!pred && !gt)) return ISDF_EINVAL;
+  if (gt && !vol) return ISDF_EINVAL;
+  if ((pred_rgb || gt_rgb) && !cmap) return ISDF_EINVAL;
+  if ((pred_cost || gt_cost) && !(chomp_eps > 0.f && __builtin_isfinite(chomp_eps))) return ISDF_EINVAL;
+  if (cmap && (cmap->n_colors < 1 || cmap->n_colors > ISDF_COLORMAP_MAX_COLORS || !(cmap->range > 0.f) ||
+               !__builtin_isfinite(cmap->range) || !__builtin_isfinite(cmap->vmin)))
+    return ISDF_EINVAL;
+  if (vol && !gt_volume_ok(vol)) return ISDF_EINVAL;
+  if (n == 0) return ISDF_OK;
+  if ((pred && !sdf) || (gt && (!pts || !vol->values)) || (cmap && (pred_rgb || gt_rgb) && !cmap->lut)) return ISDF_EINVAL;
+  // inputs nothing reads are dropped here, so the kernel's tests stay "pointer given = output wanted"
+  return launch_slice_images((pred_rgb || gt_rgb) ? cmap : nullptr, gt ? vol : nullptr, pts, pred ? sdf : nullptr, n, oob_fill,
+                             chomp_eps, pred_rgb, gt_out, gt_rgb, pred_cost, gt_cost, (hipStream_t)stream);
+}
+
+int isdf_plane_points(const float* origin, const float* du, const float* dv, int32_t H, int32_t W, float* pts_out,
+                      void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!origin || !du || !dv || H < 0 || W < 0 || (int64_t)H * W > 0x7fffffff) return ISDF_EINVAL;
+  if ((int64_t)H * W == 0) return ISDF_OK;
+  if (!pts_out) return ISDF_EINVAL;
+  return launch_plane_points(origin, du, dv, H, W, pts_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 // Both reductions are deterministic: per-block partial sums in double, combined in block order by one closing block; the
 // nearest neighbour is a minimum over integer keys (squared distance bits, then index), which no order can change.
 #include "isdf_common.h"
+#include "gt_volume_dev.h"
 
 namespace isdf {
 
@@ -29,8 +30,9 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-// One thread per point (grid-stride): grid coordinate, in-bounds test with the faces inclusive, trilinear value, validity,
-// and this point's share of the 24 sums.  Block b writes its partial record to part[b].
+// One thread per point (grid-stride): grid coordinate, in-bounds test with the faces inclusive, trilinear value (all three
+// in gt_volume_dev.h, shared with slices.hip), validity, and this point's share of the 24 sums.  Block b writes its partial
+// record to part[b].
 __global__ __launch_bounds__(256) void sdf_metrics_kernel(const isdf_gt_volume vol, const float* __restrict__ pts,
                                                           const float* __restrict__ sdf, int64_t n, int exclude_zero,
                                                           float oob_fill, float* __restrict__ gt_out,
@@ -39,27 +41,9 @@ __global__ __launch_bounds__(256) void sdf_metrics_kernel(const isdf_gt_volume v
   double acc[REC];
 #pragma unroll
   for (int v = 0; v < REC; ++v) acc[v] = 0.0;
-  const int nx = vol.nx, ny = vol.ny, nz = vol.nz;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float ux = (pts[i * 3] - vol.origin[0]) / vol.spacing[0];
-    const float uy = (pts[i * 3 + 1] - vol.origin[1]) / vol.spacing[1];
-    const float uz = (pts[i * 3 + 2] - vol.origin[2]) / vol.spacing[2];
-    const bool inb = ux >= 0.f && ux <= (float)(nx - 1) && uy >= 0.f && uy <= (float)(ny - 1) && uz >= 0.f &&
-                     uz <= (float)(nz - 1);
-    float gt = oob_fill;
-    if (inb) {
-      // cell index clamped to [0, n - 2] (a point on the upper face interpolates inside the last cell with t = 1)
-      const int ix = min((int)ux, nx - 2), iy = min((int)uy, ny - 2), iz = min((int)uz, nz - 2);
-      const float tx = ux - (float)ix, ty = uy - (float)iy, tz = uz - (float)iz;
-      const float* c = vol.values + ((int64_t)ix * ny + iy) * nz + iz;
-      const int64_t sx = (int64_t)ny * nz, sy = nz;
-      const float c00 = fmaf(tz, c[1] - c[0], c[0]);
-      const float c01 = fmaf(tz, c[sy + 1] - c[sy], c[sy]);
-      const float c10 = fmaf(tz, c[sx + 1] - c[sx], c[sx]);
-      const float c11 = fmaf(tz, c[sx + sy + 1] - c[sx + sy], c[sx + sy]);
-      const float c0 = fmaf(ty, c01 - c00, c00), c1 = fmaf(ty, c11 - c10, c10);
-      gt = fmaf(tx, c1 - c0, c0);
-    }
+    bool inb;
+    const float gt = gt_trilinear(vol, pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2], oob_fill, &inb);
     const bool valid = inb && (gt != 0.f || !exclude_zero);
     if (gt_out) gt_out[i] = gt;
     if (valid_out) valid_out[i] = valid ? 1 : 0;

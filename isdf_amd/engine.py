@@ -682,6 +682,60 @@ class Engine:
                    "isdf_nn_distance")
         return dist, index, total
 
+    # ---- SDF slice images --------------------------------------------------------------
+    def slice_images(self, pts, sdf, cmap=None, volume=None, chomp_eps=None, oob_fill=0.0):
+        """(pred_rgb u8 [n,3], gt f32 [n], gt_rgb u8 [n,3], pred_cost f32 [n], gt_cost f32 [n]) on the device, None for what was
+        not asked: isdf_slice_images, everything Trainer.compute_slices / obj_slices_vis / get_sdf_grid_pc do after the network
+        (trainer.py:1593-1639,1796-1807,1453-1461) in one pass.  sdf [n] (or None: no predicted outputs), pts [n,3] (needed with
+        `volume`); cmap: isdf_amd.slices.Colormap (or None: no colours); volume: isdf_amd.metrics.GtVolume (or None: no ground
+        truth); chomp_eps: epsilon of the CHOMP cost fields (or None).  No host synchronisation."""
+        s = None if sdf is None else sdf.detach().reshape(-1).to(device=self.device, dtype=torch.float32).contiguous()
+        p = None if pts is None else pts.detach().reshape(-1, 3).to(device=self.device, dtype=torch.float32).contiguous()
+        if s is None and p is None:
+            raise ValueError("slice_images: neither sdf nor pts")
+        n = int(s.numel() if s is not None else p.shape[0])
+        if s is not None and p is not None and int(p.shape[0]) != n:
+            raise ValueError("slice_images: %d points but %d sdf values" % (p.shape[0], n))
+        if volume is not None:
+            if p is None:
+                raise ValueError("slice_images: the ground truth needs the points")
+            vd = volume.values.device
+            if vd.type != self.device.type or (self.device.index is not None and vd.index != self.device.index):
+                raise ValueError("slice_images: the ground-truth volume is on %s, the engine on %s" % (vd, self.device))
+        cost = chomp_eps is not None
+
+        def out(want, *shape, dtype=torch.float32):
+            return torch.empty(*shape, dtype=dtype, device=self.device) if want else None
+        pred_rgb = out(s is not None and cmap is not None, n, 3, dtype=torch.uint8)
+        pred_cost = out(s is not None and cost, n)
+        gt = out(volume is not None, n)
+        gt_rgb = out(volume is not None and cmap is not None, n, 3, dtype=torch.uint8)
+        gt_cost = out(volume is not None and cost, n)
+        if all(t is None for t in (pred_rgb, pred_cost, gt)):
+            raise ValueError("slice_images: nothing to compute (no colour map, ground-truth volume or chomp_eps)")
+        if n == 0:            # empty tensors have no address to hand over; there is nothing to launch
+            return pred_rgb, gt, gt_rgb, pred_cost, gt_cost
+        cm = None if cmap is None else cmap.to_c(self.device)
+        vol = None if volume is None else volume.to_c()
+        _ffi.check(self.lib.isdf_slice_images(_ffi.ptr(p), _ffi.ptr(s), n, None if cm is None else C.byref(cm),
+                                              None if vol is None else C.byref(vol), float(oob_fill),
+                                              float(chomp_eps) if cost else 0.0, _ffi.ptr(pred_rgb), _ffi.ptr(gt), _ffi.ptr(gt_rgb),
+                                              _ffi.ptr(pred_cost), _ffi.ptr(gt_cost), _stream(self.device)), "isdf_slice_images")
+        return pred_rgb, gt, gt_rgb, pred_cost, gt_cost
+
+    def plane_points(self, origin, du, dv, H, W):
+        """[H, W, 3] on the device: isdf_plane_points, p[i][j] = (origin + i * du) + j * dv with every operation rounded to fp32
+        (origin, du, dv: three numbers each, on the host)."""
+        H, W = int(H), int(W)
+        if H < 0 or W < 0:
+            raise ValueError("plane_points: H and W must be >= 0 (got %d, %d)" % (H, W))
+        vec = [(C.c_float * 3)(*[float(x) for x in np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, np.float64).reshape(3)])
+               for v in (origin, du, dv)]
+        pts = torch.empty(H, W, 3, dtype=torch.float32, device=self.device)
+        _ffi.check(self.lib.isdf_plane_points(vec[0], vec[1], vec[2], H, W, _ffi.ptr(pts), _stream(self.device)),
+                   "isdf_plane_points")
+        return pts
+
     # ---- AdamW ----------------------------------------------------------------------
     def adamw(self, lr=0.0013, weight_decay=0.012, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0,
               use_device_count=True):
