@@ -514,6 +514,49 @@ int isdf_sdf_metrics(const isdf_gt_volume* vol, const float* pts, const float* s
                      float oob_fill, double* record, float* gt_out, uint8_t* valid_out, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* The arithmetic of eval_pts.fixed_pts_eval after the network (eval_pts.py:96-299) in ONE pass over n points, for the two
+ * nested regions it reports ("vis": every visible point, "vox": the part another mapper also covers): the |sdf - gt| figures
+ * of isdf_sdf_metrics per region, and the mean cosine distance between the predicted gradient and the central-difference
+ * gradient of the ground truth (eval_pts.eval_grad(..., delta, is_gt_sdf=True), eval_pts.py:68-93).
+ * flags [n] u8 (optional): bit 1 = in the vis sdf set, 2 = vox sdf set, 4 = vis gradient set, 8 = vox gradient set.  NULL: every
+ * point is in both sdf sets and in no gradient set.  Bits 4 and 8 are honoured only when grad_sets != 0.
+ * Ground truth from exactly one of: `vol` (trilinear lookup; its grid spacing and origin are read from the DOUBLES of this
+ * struct, not from vol's fp32 fields), or `gt_in` [n] doubles on the device (every point counts as in bounds, no lookup; the
+ * full-volume leg, whose ground truth comes from a file).  gt_in excludes gradient sets.
+ * ALL arithmetic is double -- grid coordinate, in-bounds test (faces inclusive), trilinear blend, sums -- on the fp32 points
+ * widened: the reference evaluates these in float64.
+ * records: 2 x ISDF_REGION_RECORD doubles on the device, vis then vox:
+ *   [0..23]  the fields of isdf_sdf_metrics over the set's points with valid = in bounds (zero-valued ground truth is KEPT, as
+ *            eval_pts.sub_eval keeps it); the bins compare the double ground truth with the double limits
+ *   [24]     points in the set's gradient set
+ *   [25]     sum of 1 - cos over those whose ground-truth gradient is finite, cos = x.y / (max(|x|, 1e-6) * max(|y|, 1e-6))
+ *            (torch.nn.CosineSimilarity(dim=1, eps=1e-6)) with the fp32 predicted gradient x widened
+ *   [26]     points of [24] whose ground-truth gradient is not finite (one of its six lookups at p +- delta e_i is out of
+ *            bounds or == 0): the reference's mean is then NaN
+ * The records are bit-identical from run to run (per-block partial records combined in block order, a grid that depends on n
+ * alone, no float atomics).  workspace: ISDF_REGION_METRICS_WS_BYTES, no initialisation needed.  n = 0 writes zero records.
+ * ISDF_EINVAL: no ground-truth source, or both; grad_sets without sdf_grad; grad_sets together with gt_in; delta <= 0 or
+ * not finite; a spacing <= 0.                                                                                          */
+typedef struct isdf_region_args {
+  const float* pts;           /* [n,3] fp32                                              */
+  const float* sdf;           /* [n]   fp32, the prediction                              */
+  const float* sdf_grad;      /* [n,3] fp32 or NULL                                      */
+  const uint8_t* flags;       /* [n] or NULL                                             */
+  const isdf_gt_volume* vol;  /* or NULL (host pointer, read before the call returns)    */
+  const double* gt_in;        /* [n] on the device, or NULL                              */
+  int64_t n;
+  int32_t grad_sets;          /* != 0: flag bits 4 and 8 select gradient points          */
+  int32_t reserved;
+  double spacing[3];          /* of vol's grid, > 0 (ignored with gt_in)                 */
+  double origin[3];
+  double delta;               /* > 0: half the central-difference step (0.01)            */
+} isdf_region_args;
+
+#define ISDF_REGION_RECORD 27
+#define ISDF_REGION_METRICS_WS_BYTES (ISDF_METRICS_MAX_BLOCKS * 2 * ISDF_REGION_RECORD * 8)
+
+int isdf_region_metrics(const isdf_region_args* args, double* records, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Exact nearest-neighbour distances, the KD-tree queries of metrics.accuracy / completion (metrics.py:48-59), by brute
  * force: dist[q] = min over t of |query[q] - target[t]| for query [n,3] and target [m,3] (m >= 1), fp32 on the device.
  * The squared distance is (dx*dx + dy*dy) + dz*dz of the coordinate DIFFERENCES, each operation rounded to fp32, and

@@ -21,7 +21,7 @@ SYMBOLS = [
     "isdf_sdf_eval", "isdf_train_step", "isdf_train_step_adamw", "isdf_train_step_finish", "isdf_bounds_pc",
     "isdf_frame_avg", "isdf_adamw", "isdf_estimate_normals", "isdf_render_depth", "isdf_allreduce_sum_f32",
     "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables", "isdf_render_ws_bytes", "isdf_render_views",
-    "isdf_sdf_metrics", "isdf_nn_distance", "isdf_slice_images", "isdf_plane_points",
+    "isdf_sdf_metrics", "isdf_nn_distance", "isdf_slice_images", "isdf_plane_points", "isdf_region_metrics",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -109,6 +109,13 @@ class GtVolumeArgs(C.Structure):
                 ("spacing", C.c_float * 3), ("origin", C.c_float * 3)]
 
 
+class RegionArgs(C.Structure):
+    """isdf_region_args"""
+    _fields_ = [("pts", C.c_void_p), ("sdf", C.c_void_p), ("sdf_grad", C.c_void_p), ("flags", C.c_void_p),
+                ("vol", C.POINTER(GtVolumeArgs)), ("gt_in", C.c_void_p), ("n", C.c_int64), ("grad_sets", C.c_int32),
+                ("reserved", C.c_int32), ("spacing", C.c_double * 3), ("origin", C.c_double * 3), ("delta", C.c_double)]
+
+
 class ColormapArgs(C.Structure):
     _fields_ = [("lut", C.c_void_p), ("n_colors", C.c_int32), ("vmin", C.c_float), ("range", C.c_float)]
 
@@ -116,6 +123,9 @@ class ColormapArgs(C.Structure):
 COLORMAP_MAX_COLORS = 16381                           # ISDF_COLORMAP_MAX_COLORS
 METRICS_RECORD = 24                                   # ISDF_METRICS_RECORD (doubles)
 SDF_METRICS_WS_BYTES = 1024 * METRICS_RECORD * 8      # ISDF_SDF_METRICS_WS_BYTES
+REGION_RECORD = 27                                    # ISDF_REGION_RECORD (doubles per set; a call writes two)
+REGION_METRICS_WS_BYTES = 1024 * 2 * REGION_RECORD * 8    # ISDF_REGION_METRICS_WS_BYTES
+FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
 
 
 def nn_ws_bytes(n):
@@ -178,6 +188,7 @@ def lib():
     L.isdf_nn_distance.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]
     L.isdf_slice_images.argtypes = [vp, vp, i64, P(ColormapArgs), P(GtVolumeArgs), f32, f32, vp, vp, vp, vp, vp, vp]
     L.isdf_plane_points.argtypes = [P(f32), P(f32), P(f32), i32, i32, vp, vp]
+    L.isdf_region_metrics.argtypes = [P(RegionArgs), vp, vp, i64, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64

@@ -48,6 +48,7 @@ int launch_normal_points(const float* T_WC, const float* dirs_C, int64_t R, int6
 int launch_normal_finish(const float* T_WC, int64_t R, int64_t n_rays, const float* grad, float* normals, hipStream_t st);
 int launch_sdf_metrics(const isdf_gt_volume& vol, const float* pts, const float* sdf, int64_t n, int exclude_zero,
                        float oob_fill, double* record, float* gt_out, uint8_t* valid_out, double* part, hipStream_t st);
+int launch_region_metrics(const isdf_region_args& a, double* records, double* part, hipStream_t st);
 int launch_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
                        double* dist_sum, unsigned long long* keys, double* part, hipStream_t st);
 int launch_slice_images(const isdf_colormap* cmap, const isdf_gt_volume* vol, const float* pts, const float* sdf, int64_t n,
@@ -497,6 +498,23 @@ int isdf_sdf_metrics(const isdf_gt_volume* vol, const float* pts, const float* s
   if (!workspace || workspace_bytes < ISDF_SDF_METRICS_WS_BYTES) return ISDF_EWORKSPACE;
   return launch_sdf_metrics(*vol, pts, sdf, n, exclude_zero_gt != 0, oob_fill, record, gt_out, valid_out, (double*)workspace,
                             (hipStream_t)stream);
+}
+
+int isdf_region_metrics(const isdf_region_args* a, double* records, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!a || !records || a->n < 0 || a->n > ((int64_t)1 << 40)) return ISDF_EINVAL;
+  if ((a->vol != nullptr) == (a->gt_in != nullptr)) return ISDF_EINVAL;          // exactly one ground-truth source
+  if (a->grad_sets && (!a->sdf_grad || a->gt_in)) return ISDF_EINVAL;
+  if (!(a->delta > 0.0) || !__builtin_isfinite(a->delta)) return ISDF_EINVAL;
+  if (a->vol) {
+    if (!gt_volume_ok(a->vol)) return ISDF_EINVAL;
+    for (int k = 0; k < 3; ++k)
+      if (!(a->spacing[k] > 0.0) || !__builtin_isfinite(a->spacing[k]) || !__builtin_isfinite(a->origin[k])) return ISDF_EINVAL;
+    if (a->n > 0 && !a->vol->values) return ISDF_EINVAL;
+  }
+  if (a->n > 0 && (!a->pts || !a->sdf)) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < ISDF_REGION_METRICS_WS_BYTES) return ISDF_EWORKSPACE;
+  return launch_region_metrics(*a, records, (double*)workspace, (hipStream_t)stream);
 }
 
 int isdf_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,

@@ -100,6 +100,116 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restr
   }
 }
 
+// ---- region metrics (eval_pts.fixed_pts_eval, eval_pts.py:96-299) -------------------------------------------------------
+// One thread per point (grid-stride), everything in double.  A point's flag byte says which of the two sets (vis, vox) count its
+// |sdf - gt| figures (bits 1, 2) and its cosine distance (bits 4, 8).  The point's own contribution is formed once, in
+// registers, and added to each set's accumulators under a select: both sets are indexed statically, nothing lives in scratch.
+constexpr int RREC = ISDF_REGION_RECORD;
+
+// one lookup of eval_pts.eval_grad(is_gt_sdf=True): NaN out of bounds or where the value is == 0 (eval_pts.py:79-82)
+__device__ __forceinline__ double grad_lookup(const isdf_gt_volume& vol, const isdf_region_args& a, double x, double y, double z) {
+  bool inb;
+  const double f = gt_trilinear_f64(vol, a.spacing, a.origin, x, y, z, &inb);
+  return (inb && f != 0.0) ? f : __builtin_nan("");
+}
+
+__global__ __launch_bounds__(256) void region_metrics_kernel(const isdf_gt_volume vol, const isdf_region_args a, int has_vol,
+                                                             double* __restrict__ part) {
+  __shared__ double sh[4][2 * RREC];
+  double acc[2][RREC];
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int v = 0; v < RREC; ++v) acc[k][v] = 0.0;
+  const float* __restrict__ pts = a.pts;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+    const unsigned f = (a.flags ? a.flags[i] : 3u) & (a.grad_sets ? 15u : 3u);
+    double c[RREC];
+#pragma unroll
+    for (int v = 0; v < RREC; ++v) c[v] = 0.0;
+    const double px = (double)pts[i * 3], py = (double)pts[i * 3 + 1], pz = (double)pts[i * 3 + 2];
+    if (f & 3u) {
+      bool inb = true;
+      double g;
+      if (has_vol) g = gt_trilinear_f64(vol, a.spacing, a.origin, px, py, pz, &inb);
+      else g = a.gt_in[i];
+      if (inb) {
+        const double s = (double)a.sdf[i];
+        const double d = fabs(s - g);
+        c[0] = 1.0; c[1] = 1.0; c[2] = d;
+        // metrics.binned_losses on the float64 ground truth: limits -inf, 0, 0.1, 0.2, 0.5, 1, +inf, strict on both sides
+        const double lim[7] = {-INFINITY, 0.0, 0.1, 0.2, 0.5, 1.0, INFINITY};
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+          const bool in = g > lim[b] && g < lim[b + 1];
+          c[3 + b] = in ? d : 0.0;
+          c[9 + b] = in ? 1.0 : 0.0;
+        }
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+          const double eps = 1.0 + 0.5 * e;
+          const double cp = chomp(s, eps), cg = chomp(g, eps);
+          c[15 + 3 * e] = fabs(cp - cg);
+          c[16 + 3 * e] = cp;
+          c[17 + 3 * e] = cg;
+        }
+      }
+    }
+    if (f & 12u) {
+      // eval_pts.eval_grad: grad_i = (f(p + d e_i) - f(p - d e_i)) / (2 d), six lookups at (double)p +- delta
+      const double dl = a.delta;
+      const double gx = (grad_lookup(vol, a, px + dl, py, pz) - grad_lookup(vol, a, px - dl, py, pz)) / (2.0 * dl);
+      const double gy = (grad_lookup(vol, a, px, py + dl, pz) - grad_lookup(vol, a, px, py - dl, pz)) / (2.0 * dl);
+      const double gz = (grad_lookup(vol, a, px, py, pz + dl) - grad_lookup(vol, a, px, py, pz - dl)) / (2.0 * dl);
+      c[24] = 1.0;
+      if (isfinite(gx) && isfinite(gy) && isfinite(gz)) {
+        // torch.nn.CosineSimilarity(dim=1, eps=1e-6): x.y / (max(|x|, eps) * max(|y|, eps))
+        const double x0 = (double)a.sdf_grad[i * 3], x1 = (double)a.sdf_grad[i * 3 + 1], x2 = (double)a.sdf_grad[i * 3 + 2];
+        const double nx = sqrt((x0 * x0 + x1 * x1) + x2 * x2), ny = sqrt((gx * gx + gy * gy) + gz * gz);
+        const double cs = ((x0 * gx + x1 * gy) + x2 * gz) / (fmax(nx, 1e-6) * fmax(ny, 1e-6));
+        c[25] = 1.0 - cs;
+      } else {
+        c[26] = 1.0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const bool in_sdf = (f >> k) & 1u, in_grad = (f >> (2 + k)) & 1u;
+#pragma unroll
+      for (int v = 0; v < 24; ++v) acc[k][v] += in_sdf ? c[v] : 0.0;
+#pragma unroll
+      for (int v = 24; v < RREC; ++v) acc[k][v] += in_grad ? c[v] : 0.0;
+    }
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int v = 0; v < RREC; ++v) {
+      const double t = wave_sum(acc[k][v]);
+      if (lane == 0) sh[wave][k * RREC + v] = t;
+    }
+  __syncthreads();
+  if (threadIdx.x < 2 * RREC)
+    part[(int64_t)blockIdx.x * (2 * RREC) + threadIdx.x] =
+        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
+int launch_region_metrics(const isdf_region_args& a, double* records, double* part, hipStream_t st) {
+  // as launch_sdf_metrics: the grid is a function of n alone
+  int64_t blocks = (a.n + 255) / 256;
+  if (blocks > MAXB) blocks = MAXB;
+  if (blocks > 0) {
+    isdf_gt_volume vol = {};
+    if (a.vol) vol = *a.vol;
+    hipLaunchKernelGGL(region_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, st, vol, a, a.vol ? 1 : 0, part);
+    const int rc = isdf_launch_status();
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, part, blocks, 2 * RREC, records);
+  return isdf_launch_status();
+}
+
 // ---- nearest neighbour, brute force -----------------------------------------------------------------------------------
 // Block (x, y): NN_Q queries per thread (1024 per block) against target chunk y.  A tile of NN_TILE targets sits in LDS one
 // axis per array, four targets per float4: every lane reads the SAME address (a broadcast ds_read_b128, no bank conflict),

@@ -35,4 +35,32 @@ __device__ __forceinline__ float gt_trilinear(const isdf_gt_volume& vol, float p
   return gt;
 }
 
+// The same lookup in double, for isdf_region_metrics (eval.hip): the reference evaluates eval_pts.fixed_pts_eval's ground truth
+// and its central differences in float64 on the fp32 points.  spacing / origin are the grid's doubles (the struct's own are
+// fp32); the values are the volume's fp32 ones, widened.  Returns NaN out of bounds.
+__device__ __forceinline__ double gt_trilinear_f64(const isdf_gt_volume& vol, const double* spacing, const double* origin,
+                                                   double px, double py, double pz, bool* inb_out) {
+  const int nx = vol.nx, ny = vol.ny, nz = vol.nz;
+  const double ux = (px - origin[0]) / spacing[0];
+  const double uy = (py - origin[1]) / spacing[1];
+  const double uz = (pz - origin[2]) / spacing[2];
+  const bool inb = ux >= 0.0 && ux <= (double)(nx - 1) && uy >= 0.0 && uy <= (double)(ny - 1) && uz >= 0.0 &&
+                   uz <= (double)(nz - 1);
+  double gt = __builtin_nan("");
+  if (inb) {
+    const int ix = min((int)ux, nx - 2), iy = min((int)uy, ny - 2), iz = min((int)uz, nz - 2);
+    const double tx = ux - (double)ix, ty = uy - (double)iy, tz = uz - (double)iz;
+    const float* c = vol.values + ((int64_t)ix * ny + iy) * nz + iz;
+    const int64_t sx = (int64_t)ny * nz, sy = nz;
+    const double v000 = c[0], v001 = c[1], v010 = c[sy], v011 = c[sy + 1];
+    const double v100 = c[sx], v101 = c[sx + 1], v110 = c[sx + sy], v111 = c[sx + sy + 1];
+    const double c00 = v000 + tz * (v001 - v000), c01 = v010 + tz * (v011 - v010);
+    const double c10 = v100 + tz * (v101 - v100), c11 = v110 + tz * (v111 - v110);
+    const double c0 = c00 + ty * (c01 - c00), c1 = c10 + ty * (c11 - c10);
+    gt = c0 + tx * (c1 - c0);
+  }
+  *inb_out = inb;
+  return gt;
+}
+
 }  // namespace isdf

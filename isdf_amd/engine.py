@@ -202,6 +202,7 @@ class Engine:
         self._mesher = None       # marching-cubes workspace, count pair and output capacity (isdf_amd.mesh.Mesher)
         self._renderer = None     # rendered-view workspace (isdf_amd.render.Renderer)
         self._eval_ws = None      # partial records of isdf_sdf_metrics
+        self._region_ws = None    # ... and of isdf_region_metrics
         self._nn_ws = None        # keys and partial sums of isdf_nn_distance
         self.reduce_buf = None
         self.reduce_extra = 0
@@ -661,6 +662,56 @@ class Engine:
                                              _ffi.ptr(self._eval_ws), int(self._eval_ws.numel()), _stream(self.device)),
                    "isdf_sdf_metrics")
         return record, gt, valid
+
+    def region_metrics(self, pts, sdf, volume=None, gt=None, sdf_grad=None, flags=None, delta=0.01, out=None):
+        """records f64 [2, 27] on the device (vis, vox): isdf_region_metrics, the arithmetic of eval_pts.fixed_pts_eval after the
+        network (eval_pts.py:96-299) in one pass, all in double.  pts [n,3], sdf [n]; ground truth from `volume`
+        (isdf_amd.metrics.GtVolume) or from `gt` (float64 [n], the full-volume leg); flags u8 [n] (_ffi.FLAG_*; None: every point
+        in both sdf sets); sdf_grad [n,3]: the gradient sets named by flag bits 4 / 8 are evaluated.  out: a [2, 27] float64 view
+        to write into (several legs, one copy).  No host synchronisation."""
+        dev = self.device
+        p = pts.detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
+        s = sdf.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        n = int(p.shape[0])
+        if s.numel() != n:
+            raise ValueError("region_metrics: %d points but %d sdf values" % (n, s.numel()))
+        if (volume is None) == (gt is None):
+            raise ValueError("region_metrics: exactly one of volume and gt")
+        a = _ffi.RegionArgs()
+        keep = [p, s]
+        if volume is not None:
+            vd = volume.values.device
+            if vd.type != dev.type or (dev.index is not None and vd.index != dev.index):
+                raise ValueError("region_metrics: the ground-truth volume is on %s, the engine on %s" % (vd, dev))
+            vc = volume.to_c()
+            keep.append(vc)
+            a.vol = C.pointer(vc)
+            for k in range(3):
+                a.spacing[k], a.origin[k] = volume.spacing[k], volume.origin[k]
+        else:
+            g = gt.detach().reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+            if g.numel() != n:
+                raise ValueError("region_metrics: %d points but %d ground-truth values" % (n, g.numel()))
+            keep.append(g)
+            a.gt_in = g.data_ptr() if n else 8        # n = 0: an empty tensor has no address; nothing is read
+        for name, t, dt, width in (("sdf_grad", sdf_grad, torch.float32, 3), ("flags", flags, torch.uint8, 1)):
+            if t is not None:
+                t = t.detach().reshape(-1).to(device=dev, dtype=dt).contiguous()
+                if t.numel() != n * width:
+                    raise ValueError("region_metrics: %s has %d elements for %d points" % (name, t.numel(), n))
+                keep.append(t)
+                setattr(a, name, t.data_ptr() if n else 8)
+        a.pts, a.sdf, a.n = p.data_ptr(), s.data_ptr(), n
+        a.grad_sets, a.delta = int(sdf_grad is not None), float(delta)
+        if self._region_ws is None:
+            self._region_ws = torch.empty(_ffi.REGION_METRICS_WS_BYTES, dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(2, _ffi.REGION_RECORD, dtype=torch.float64, device=dev)
+        elif out.dtype != torch.float64 or out.numel() != 2 * _ffi.REGION_RECORD or not out.is_contiguous():
+            raise ValueError("region_metrics: out must be a contiguous float64 [2, %d]" % _ffi.REGION_RECORD)
+        _ffi.check(self.lib.isdf_region_metrics(C.byref(a), _ffi.ptr(out), _ffi.ptr(self._region_ws),
+                                                int(self._region_ws.numel()), _stream(dev)), "isdf_region_metrics")
+        return out
 
     def nn_distance(self, query, target, want_index=False):
         """(dist [n] f32, index [n] i32 or None, dist_sum f64[1]) on the device: isdf_nn_distance, the exact distance from every

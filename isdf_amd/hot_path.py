@@ -20,6 +20,9 @@ reference `isdf.modules.trainer.Trainer` INSTANCE to the HIP kernels behind the 
     Trainer.eval_object_sdf     trainer.py:1955-2008 (resident frames; per visible object one isdf_sdf_metrics call)
     Trainer.eval_traj_cost      trainer.py:2010-2052 (validity count and both CHOMP sums from one record)
     Trainer.eval_mesh           trainer.py:2054-2064 (accuracy / completion by isdf_nn_distance instead of two host KD-trees)
+    Trainer.eval_fixed          trainer.py:2080-2088 (eval_pts.fixed_pts_eval, eval_pts.py:96-299: resident frames, ONE sampler launch
+                                                      for both point sets, one isdf_region_metrics pass per leg -- region masks,
+                                                      central-difference ground-truth gradient, cosine distance --, one copy back)
     Trainer.compute_slices      trainer.py:1558-1707 (all slices in one forward launch; colours, ground truth and CHOMP cost fields in
                                                       ONE isdf_slice_images pass, one copy back; write_slices / slices_vis follow)
     Trainer.obj_slices_vis      trainer.py:1775-1815 (per object one forward launch and one isdf_slice_images pass)
@@ -35,7 +38,7 @@ reference's state_dict keys whose parameters are views of one flat buffer), `tra
 with the `torch.optim.AdamW` surface, `trainer.frames` an `isdf_amd.frame_store.FrameData` (the reference's fields and
 `add_frame_data` contract on geometrically growing buffers instead of one `torch.cat` of the whole keyframe set per frame,
 data_util.py:84-102; the existing keyframes migrate).  Everything else (`add_frame`, `add_data`,
-`check_keyframe_latest`, `select_keyframes`, `eval_fixed`, `eval_sdf_volume`, the remaining visualisation)
+`check_keyframe_latest`, `select_keyframes`, `eval_sdf_volume`, the remaining visualisation)
 keeps running as the reference's own code on the same object.
 
 Where the reference is not importable (the GPU box, bench.py), `bench_support/standin_trainer.py` (test / bench infrastructure, outside
@@ -48,6 +51,7 @@ import ctypes
 import os
 import sys
 import types
+import warnings
 
 import numpy as np
 import torch
@@ -713,21 +717,27 @@ class HotPath:
             c = hip.gt_volume = (itp, GtVolume.from_interpolator(itp, hip.device))
         return c[1]
 
-    def _eval_frames(self):
+    def _eval_frames(self, upto=None):
         """(depth_batch [F,H,W], T_WC_batch [F,4,4]) of the cached sequence up to the virtual clock, as eval_sdf_visible and
         eval_object_sdf build them (trainer.py:1869-1875,1968-1974) -- but RESIDENT: the reference converts and uploads the whole
         sequence on every call (2 GB at 600 frames of 680 x 1200); here only the frames not yet on the device are read from
         `self.cached_dataset` and copied.  Incremental runs ask for arange(int(tot_step_time * fps)), which only grows; the
         non-incremental get_all() is uploaded once.  The cache lives on self._hip (not in hip_state_dict); drop_eval_cache()
-        releases it; a clock that went backwards or another dataset object starts it afresh."""
+        releases it; a clock that went backwards or another dataset object starts it afresh.
+        upto: the frames of cached_dataset[arange(upto)] instead of the clock's (eval_fixed: its timestamp is normally behind the
+        clock, so this is a prefix of what is held; frames beyond what is held are uploaded, once)."""
         hip = self._hip
         ds = self.cached_dataset
         c = getattr(hip, "eval_cache", None)
         mode = "incremental" if self.incremental else "all"
         want = int(self.tot_step_time * self.fps) if self.incremental else 0
-        if c is None or c.dataset is not ds or c.mode != mode or want < c.asked:
-            c = hip.eval_cache = types.SimpleNamespace(dataset=ds, mode=mode, asked=0, held=0, depth=None, T=None,
+        if c is None or c.dataset is not ds or c.mode != mode or (upto is None and want < c.clock):
+            c = hip.eval_cache = types.SimpleNamespace(dataset=ds, mode=mode, asked=0, clock=0, held=0, depth=None, T=None,
                                                        uploaded_frames=0, uploaded_bytes=0)
+        if upto is None:
+            c.clock = want
+        else:
+            want = int(upto)
         if mode == "all":
             if c.depth is None:
                 sample = ds.get_all()
@@ -738,7 +748,13 @@ class HotPath:
             c.asked = want
         if c.depth is None:                      # no frame yet: the reference's empty batch (its rays_per_frame then divides by 0)
             return (torch.zeros(0, self.H, self.W, device=hip.device), torch.zeros(0, 4, 4, device=hip.device))
-        return c.depth[:c.held], c.T[:c.held]
+        held = c.held
+        if (mode == "all" and upto is not None) or (mode != "all" and want < c.asked):
+            # a prefix: the frames with an index below `want` (SceneCache.__getitem__ keeps those in keep_ixs, dataset.py:251-257)
+            keep = getattr(ds, "keep_ixs", None)
+            k = int(np.searchsorted(np.asarray(keep), want)) if keep is not None else min(want, len(ds))
+            held = min(k, c.held)
+        return c.depth[:held], c.T[:held]
 
     def _eval_cache_append(self, c, depth, T):
         """new frames -> the resident buffers (capacity grows by half, never beyond the dataset's length when it has one)"""
@@ -867,6 +883,148 @@ class HotPath:
         rec_pc = ref.trimesh.sample.sample_surface(sdf_mesh, samples)
         gt_pc = ref.trimesh.sample.sample_surface(mesh_gt, samples)
         return metrics.accuracy_completion(self.engine, gt_pc[0], rec_pc[0])
+
+    # ------------------------------------------------------------------ fixed-point evaluation (trainer.py:2080-2088)
+    @staticmethod
+    def _region_flags(valid_gt_sdf, valid_vox_sdf, valid_gt_grad=None):
+        """flag byte per drawn point (_ffi.FLAG_*) from the mask files of one point set, eval_pts.py:130-152 written out:
+        A = valid_gt_sdf [N] selects the vis sdf set, valid_vox_sdf [A.sum()] the vox subset of it; G = valid_gt_grad [N] the vis
+        gradient set, and the vox gradient set is A & B & G with B scattered back to the N points."""
+        A = np.asarray(valid_gt_sdf, bool).reshape(-1)
+        B = np.zeros(A.shape[0], bool)
+        B[A] = np.asarray(valid_vox_sdf, bool).reshape(-1)
+        flags = A * np.uint8(_ffi.FLAG_VIS_SDF) + (A & B) * np.uint8(_ffi.FLAG_VOX_SDF)
+        if valid_gt_grad is not None:
+            G = np.asarray(valid_gt_grad, bool).reshape(-1)
+            flags = flags + G * np.uint8(_ffi.FLAG_VIS_GRAD) + (A & B & G) * np.uint8(_ffi.FLAG_VOX_GRAD)
+        return flags.astype(np.uint8)
+
+    def eval_fixed(self):
+        """The reference's nested dict (eval_pts.fixed_pts_eval, eval_pts.py:96-299) at the next timestamp of `self.eval_times`.
+        Frames from the resident cache; the pixels and the one stratified draw on the torch CPU generator exactly as
+        eval_pts.sample_rays draws them (the mask files are aligned index for index with these draws), whatever graft(rng=...)
+        says; ONE sampler launch gives both point sets (column 0 of pc: sample_surface's, column 1: sample_visible_region's); one
+        forward-with-gradient launch for the visible region, one forward for surface, objects and volume together; one
+        isdf_region_metrics pass per leg into one records tensor, ONE copy back.  Two host synchronisations: the sampler's
+        n_valid and that copy.  The Philox counter does not advance; afterwards the torch CPU generator and numpy's global one are
+        where the reference leaves them.  Deviations: the visible region's sdf comes from the gradient-returning
+        kernel; a mask-selected point outside the ground-truth grid is left out (the reference averages its 1e99 fill value in)
+        with one warning; the object points are rounded to fp32 before the ground-truth lookup."""
+        from . import metrics
+        if self.dataset_format not in ("replicaCAD", "ScanNet"):       # the reference's own method (it fails there too)
+            return super().eval_fixed()
+        t = self.eval_times.pop(0)
+        t_str = f"{t:.3f}"
+        pts_dir = os.path.join(self.eval_pts_dir, t_str)
+        masks_dir = self.eval_pts_dir + t_str
+        surf_valid_gt_sdf = np.load(masks_dir + "/surf_valid_gt_sdf.npy")
+        surf_valid_vox_sdf = np.load(masks_dir + "/surf_valid_vox_sdf.npy")
+        vis_valid_gt_sdf = np.load(masks_dir + "/vis_valid_gt_sdf.npy")
+        vis_valid_vox_sdf = np.load(masks_dir + "/vis_valid_vox_sdf.npy")
+        vis_valid_gt_grad = np.load(masks_dir + "/vis_valid_gt_grad.npy")
+        vis_valid_vox_grad = np.load(masks_dir + "/vis_valid_vox_grad.npy")
+        assert surf_valid_gt_sdf.sum() == surf_valid_vox_sdf.shape[0]
+        assert vis_valid_gt_sdf.sum() == vis_valid_vox_sdf.shape[0]
+        assert vis_valid_gt_grad.sum() == vis_valid_vox_grad.shape[0]
+
+        eng, dev = self.engine, self._hip.device
+        upto = int(min(np.floor(t * 30), len(self.scene_dataset)))
+        depth_batch, T_WC_batch = self._eval_frames(upto)
+        F, H, W = (int(v) for v in depth_batch.shape)
+
+        # eval_pts.sample_rays' draws (eval_pts.py:354-393): seed, randint h, randint w, rand(n_valid, 1)
+        torch.manual_seed(float(t_str) * 1e3)
+        rays_per_frame = 200000 // F
+        ih = torch.randint(0, H, (rays_per_frame * F,))
+        iw = torch.randint(0, W, (rays_per_frame * F,))
+        after_pixels = torch.get_rng_state()      # where sample_surface, the reference's last seeded call, leaves the generator
+        ih_d, iw_d = ih.to(dev), iw.to(dev)
+        ib_d = torch.arange(F, device=dev).repeat_interleave(rays_per_frame)
+        R = int((depth_batch[ib_d, ih_d, iw_d] != 0).sum().item())           # host synchronisation 1 of 2
+        U = torch.rand(R, 1)
+        torch.set_rng_state(after_pixels)
+        sc = self._sample_cfg(n_rays=rays_per_frame, dist_behind_surf=0. if self.dataset_format == "ScanNet" else 0.1,
+                              n_strat=1, n_surf=1)
+        sc.min_depth, sc.H, sc.W = 0.1, H, W
+        s = eng.sample(depth_batch.contiguous(), T_WC_batch.contiguous(), None,
+                       torch.arange(F, dtype=torch.int32, device=dev), None, sc,
+                       draws=dict(indices_h=ih_d, indices_w=iw_d, U=U, N_off=torch.zeros(R, 0)), want_T=False)
+        pc = s["pc"][:R]
+        surf_pts, vis_pts = pc[:, 0], pc[:, 1]
+        if vis_valid_gt_sdf.shape[0] != R or vis_valid_gt_grad.shape[0] != R or surf_valid_gt_sdf.shape[0] != R:
+            raise IndexError("eval_fixed: the mask files of %s hold %d / %d / %d entries for %d drawn points"
+                             % (masks_dir, vis_valid_gt_sdf.shape[0], vis_valid_gt_grad.shape[0], surf_valid_gt_sdf.shape[0], R))
+        vis_flags = self._region_flags(vis_valid_gt_sdf, vis_valid_vox_sdf, vis_valid_gt_grad)
+        surf_flags = self._region_flags(surf_valid_gt_sdf, surf_valid_vox_sdf)
+
+        # objects (eval_pts.py:204-258): 10000 seeded points per box, only where the timestamp directory has files for it
+        obj_legs = None
+        obj_bounds_file = self.seq_dir + '/obj_bounds.txt'
+        if os.path.exists(obj_bounds_file):
+            obj_bounds = np.loadtxt(obj_bounds_file).reshape(-1, 2, 3)          # eval_pts.load_obj_bounds
+            obj_bounds[:, 1] += 0.08
+            obj_bounds[:, 0, 0] -= 0.08
+            obj_bounds[:, 0, 2] -= 0.08
+            obj_legs = []
+            listing = os.listdir(pts_dir)
+            for i, bounds in enumerate(obj_bounds):
+                if len([x for x in listing if f'obj{i}' in x]) == 0:
+                    continue
+                valid_gt_sdf = np.load(masks_dir + f"/obj{i}_valid_gt_sdf.npy")
+                valid_vox_sdf = np.load(masks_dir + f"/obj{i}_valid_vox_sdf.npy")
+                np.random.seed(0)                                                # eval_pts.object_eval_pts
+                offsets = np.random.rand(10000, 3)
+                pts = (bounds[0] + offsets * (bounds[1] - bounds[0])[None, :])[valid_gt_sdf]
+                fl = np.uint8(_ffi.FLAG_VIS_SDF) + np.asarray(valid_vox_sdf, bool) * np.uint8(_ffi.FLAG_VOX_SDF)
+                obj_legs.append((torch.from_numpy(pts.astype(np.float32)), torch.from_numpy(fl.astype(np.uint8))))
+
+        # full volume (eval_pts.py:260-297)
+        seq = [x for x in self.seq_dir.split('/') if x != ""][-1]
+        if self.dataset_format == "replicaCAD":
+            vol_pts_file = self.eval_pts_root + "full_vol/replicaCAD.npy"
+        else:
+            vol_pts_file = self.eval_pts_root + f"full_vol/{seq}.npy"
+        gt_sdf_file = self.eval_pts_root + f"full_vol/gt_{seq}.npy"
+        vol_pts = torch.from_numpy(np.load(vol_pts_file).astype(np.float32)).reshape(-1, 3)
+        vol_gt = torch.from_numpy(np.load(gt_sdf_file).astype(np.float64)).reshape(-1)
+
+        # network: one forward-with-gradient launch (visible region), one forward launch for everything else
+        vis_sdf, vis_grad = eng.sdf_eval(vis_pts, want_grad=True)
+        parts = [surf_pts] + [p.to(dev) for p, _ in (obj_legs or [])] + [vol_pts.to(dev)]
+        rest_pts = torch.cat(parts)
+        rest_sdf = eng.sdf_eval(rest_pts)
+        bounds_ix = np.cumsum([0] + [int(p.shape[0]) for p in parts])
+
+        # metrics: one isdf_region_metrics call per leg into one records tensor, one copy back
+        vol = self._gt_volume()
+        n_obj = len(obj_legs or [])
+        records = torch.empty(3 + n_obj, 2, _ffi.REGION_RECORD, dtype=torch.float64, device=dev)
+        eng.region_metrics(vis_pts, vis_sdf, volume=vol, sdf_grad=vis_grad, flags=torch.from_numpy(vis_flags), delta=0.01,
+                           out=records[0])
+        eng.region_metrics(surf_pts, rest_sdf[:R], volume=vol, flags=torch.from_numpy(surf_flags), out=records[1])
+        selected = [[int((vis_flags & 1).sum()), int(((vis_flags >> 1) & 1).sum())],
+                    [int((surf_flags & 1).sum()), int(((surf_flags >> 1) & 1).sum())]]
+        for k, (p, fl) in enumerate(obj_legs or []):
+            a, b = bounds_ix[1 + k], bounds_ix[2 + k]
+            eng.region_metrics(rest_pts[a:b], rest_sdf[a:b], volume=vol, flags=fl, out=records[2 + k])
+            selected.append([int(p.shape[0]), int(((fl.numpy() >> 1) & 1).sum())])
+        eng.region_metrics(rest_pts[bounds_ix[-2]:], rest_sdf[bounds_ix[-2]:], gt=vol_gt, out=records[2 + n_obj])
+        host = records.cpu().numpy()                                             # host synchronisation 2 of 2
+
+        n_out = int(sum(sel[j] - host[k, j, 0] for k, sel in enumerate(selected) for j in (0, 1)))
+        if n_out:
+            warnings.warn("eval_fixed(t=%s): the mask files select %d points outside the ground-truth grid; they are left out "
+                          "(the reference averages its 1e99 fill value into the result)" % (t_str, n_out))
+        res = {"time": t}
+        res["rays"] = {"vis": metrics.RegionMetrics(host[0, 0]).as_dict(cossim=True),
+                       "vox": metrics.RegionMetrics(host[0, 1]).as_dict(cossim=True)}
+        res["visible_surf"] = {"vis": metrics.RegionMetrics(host[1, 0]).as_dict(),
+                               "vox": metrics.RegionMetrics(host[1, 1]).as_dict()}
+        if obj_legs is not None:
+            res["objects"] = [{"vis": {"av_l1": metrics.RegionMetrics(host[2 + k, 0]).sdf.av_l1},
+                               "vox": {"av_l1": metrics.RegionMetrics(host[2 + k, 1]).sdf.av_l1}} for k in range(n_obj)]
+        res["vol"] = metrics.RegionMetrics(host[2 + n_obj, 0]).as_dict()
+        return res
 
     # ------------------------------------------------------------------ SDF slices (trainer.py:1446-1481,1558-1815)
     def _slice_colormap(self, mappable):

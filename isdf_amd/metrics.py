@@ -1,9 +1,12 @@
-"""Evaluation of the map against ground truth on the device (include/isdf_hip.h: isdf_sdf_metrics, isdf_nn_distance).
+"""Evaluation of the map against ground truth on the device (include/isdf_hip.h: isdf_sdf_metrics, isdf_region_metrics,
+isdf_nn_distance).
 
     GtVolume              the ground-truth SDF grid resident on the device (what the reference keeps behind a scipy
                           RegularGridInterpolator, sdf_util.py:174-180)
     sdf_metrics           av_l1, the six distance bins and the CHOMP cost figures of Trainer.eval_sdf / eval_object_sdf /
                           eval_traj_cost (trainer.py:1831-1866,1993-2003,2026-2050): one launch pair, one host copy
+    region_metrics        the per-region figures of eval_pts.fixed_pts_eval (eval_pts.py:96-299): av_l1, bins, CHOMP, av_cossim for
+                          the vis and vox sets in one launch pair, one host copy
     accuracy_completion   metrics.accuracy / completion (metrics.py:48-59): mean nearest-neighbour distance both ways
 
 `engine` is an isdf_amd.engine.Engine (or anything with its sdf_metrics / nn_distance methods).
@@ -99,6 +102,38 @@ def sdf_metrics(engine, volume, pts, sdf, exclude_zero_gt=True):
     """SdfMetrics of predicted `sdf` [n] at `pts` [n, 3] against `volume`: one isdf_sdf_metrics call and ONE copy to the host."""
     record, _, _ = engine.sdf_metrics(volume, pts, sdf, exclude_zero_gt=exclude_zero_gt)
     return SdfMetrics(record.cpu().numpy())
+
+
+class RegionMetrics:
+    """One set (vis or vox) of an isdf_region_metrics record: `.sdf` is the SdfMetrics of its 24 leading fields, `.av_cossim` the
+    mean cosine distance over its gradient points -- NaN when any selected ground-truth gradient is not finite (what the
+    reference's .mean() gives) or when the set is empty."""
+
+    def __init__(self, record):
+        r = np.asarray(record, np.float64).reshape(-1)
+        if r.size != _ffi.REGION_RECORD:
+            raise ValueError("RegionMetrics: a record of %d doubles is needed" % _ffi.REGION_RECORD)
+        self.record = r
+        self.sdf = SdfMetrics(r[:_ffi.METRICS_RECORD])
+        self.n_grad, self.cos_dist_sum, self.n_grad_nonfinite = int(r[24]), float(r[25]), int(r[26])
+
+    @property
+    def av_cossim(self):
+        return float("nan") if self.n_grad_nonfinite else float(_ratio(self.cos_dist_sum, self.n_grad))
+
+    def as_dict(self, cossim=False):
+        """what eval_pts.sub_eval returns for the set; with `cossim` the av_cossim pair of eval_pts.py:189-190 (both entries are
+        the one figure when the gradient comes from grad_fn)"""
+        d = self.sdf.as_dict()
+        if cossim:
+            d["av_cossim"] = [self.av_cossim, self.av_cossim]
+        return d
+
+
+def region_metrics(engine, pts, sdf, volume=None, gt=None, sdf_grad=None, flags=None, delta=0.01):
+    """(vis, vox) RegionMetrics: one isdf_region_metrics call and ONE copy to the host."""
+    rec = engine.region_metrics(pts, sdf, volume=volume, gt=gt, sdf_grad=sdf_grad, flags=flags, delta=delta).cpu().numpy()
+    return RegionMetrics(rec[0]), RegionMetrics(rec[1])
 
 
 def accuracy_completion(engine, gt_points, rec_points):
