@@ -4,59 +4,9 @@
 #include <cstdio>
 #include "isdf_common.h"
 #include "chain_params.h"
+#include "launchers.h"
 
 using namespace isdf;
-
-namespace isdf {
-int launch_chain(const ChainParams& p, int mode, int64_t nTiles, hipStream_t st);
-int launch_dw(const DwParams& p, hipStream_t st);
-int launch_sample_rays(const isdf_sample_args& a, const isdf_sample_out& o, void* scan_ws, hipStream_t st);
-int64_t sample_scan_bytes(int64_t max_rays);
-int launch_adamw(float* p, float* m, float* v, const float* g, const float* cnt, float gs, float lr, float b1,
-                 float b2, float eps, float wd, int step, int64_t n, hipStream_t st);
-int launch_pack(const NetLayout& L, const float* params, uint16_t* shadow, hipStream_t st);
-int launch_adamw_pack(const NetLayout& L, float* params, float* m, float* v, uint16_t* shadow, const float* grad,
-                      const float* count_ptr, float grad_scale, float lr, float b1, float b2, float eps, float wd,
-                      int step, hipStream_t st, int n_frames = 0, const float* bl = nullptr, const float* bc = nullptr,
-                      float* la = nullptr, float* fa = nullptr, const int32_t* fa_index = nullptr,
-                      const float* loss_sums = nullptr, const float* extra = nullptr, int n_extra = 0, float* mailbox = nullptr,
-                      int fa_inline_n = 0, const int32_t* fa_inline = nullptr);
-int launch_step_tail(int phase, const NetLayout& L, const float* dwPart, const float* vecPart, int vecStride, float* grad,
-                     float* params, float* m, float* v, uint16_t* shadow, float grad_scale, float lr, float b1, float b2,
-                     float eps, float wd, int step, const float* wg_loss, int64_t maxTiles, const int32_t* n_valid, int S,
-                     const float* tot_ws, const int64_t* ib, const int64_t* ih, const int64_t* iw, int F, int H, int W,
-                     float* loss_sums, float* bl, float* bc, float* la_out, float* fa_out, const int32_t* fa_index,
-                     hipStream_t st, float* mailbox, float* extra, int n_extra, int extra_slot, float extra_value, int part = 0,
-                     int fa_inline_n = 0, const int32_t* fa_inline = nullptr);
-int launch_frame_avg(const float* bl, const float* bc, int F, float* la, float* fa, const int32_t* fa_index,
-                     hipStream_t st);
-int launch_bounds_pc(const int32_t* n_valid, int max_rays, int S, const float* pc, const float* z, const float* depth,
-                     const float* surf, int64_t n_surf, float* bounds, float* gv, hipStream_t st);
-int launch_normals(const float* depth, int H, int W, float fx, float fy, float cx, float cy, float* normals,
-                   hipStream_t st);
-int launch_render_depth(const int32_t* n_valid, int64_t n_host, int64_t max_rays, int S, const float* z,
-                        const float* sdf, const float* depth_sample, float th, float* view, int32_t* below,
-                        hipStream_t st);
-int64_t mesh_ws_layout(int64_t P, int64_t* nBlocks, int64_t* offOff, int64_t* offTot, int64_t* offVbase);
-int launch_marching_cubes(const float* vol, int32_t D0, int32_t D1, int32_t D2, float level, const float* A, const float* N,
-                          int64_t* counts, float* verts, float* normals, int64_t max_verts, int32_t* faces, int64_t max_faces,
-                          void* workspace, hipStream_t st);
-void mc_tables_host(int32_t* edge_corners, int8_t* tri_table);
-int launch_render_samples(const isdf_render_args& a, float* z, float* pc, hipStream_t st);
-int launch_normal_points(const float* T_WC, const float* dirs_C, int64_t R, int64_t n_rays, const float* depth, float* pts,
-                         hipStream_t st);
-int launch_normal_finish(const float* T_WC, int64_t R, int64_t n_rays, const float* grad, float* normals, hipStream_t st);
-int launch_sdf_metrics(const isdf_gt_volume& vol, const float* pts, const float* sdf, int64_t n, int exclude_zero,
-                       float oob_fill, double* record, float* gt_out, uint8_t* valid_out, double* part, hipStream_t st);
-int launch_region_metrics(const isdf_region_args& a, double* records, double* part, hipStream_t st);
-int launch_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
-                       double* dist_sum, unsigned long long* keys, double* part, hipStream_t st);
-int launch_slice_images(const isdf_colormap* cmap, const isdf_gt_volume* vol, const float* pts, const float* sdf, int64_t n,
-                        float oob_fill, float chomp_eps, uint8_t* pred_rgb, float* gt_out, uint8_t* gt_rgb, float* pred_cost,
-                        float* gt_cost, hipStream_t st);
-int launch_plane_points(const float* origin, const float* du, const float* dv, int32_t H, int32_t W, float* pts_out,
-                        hipStream_t st);
-}  // namespace isdf
 
 namespace isdf { thread_local int g_isdf_last_hip_error = 0; }
 
@@ -113,7 +63,7 @@ int64_t isdf_workspace_bytes(const isdf_net_cfg* net, int64_t max_points, int32_
 int64_t isdf_reduce_floats(const isdf_net_cfg* net, int32_t n_frames) {
   NetLayout l; int rc = make_layout(net, &l);
   if (rc) return rc;
-  return l.n_params + 8 + 2 * (int64_t)n_frames * 64;
+  return reduce_layout(l, n_frames).total;
 }
 
 int64_t isdf_reduce_split_floats(const isdf_net_cfg* net) {
@@ -173,6 +123,28 @@ int isdf_sdf_eval(const isdf_net_cfg* net, const float* params, const void* shad
   return launch_chain(p, mode, w.nTiles, (hipStream_t)stream);
 }
 
+// The checks every entry point that takes isdf_optim_args shares; n_frames: the window the inline index list must cover
+static bool optim_args_ok(const isdf_optim_args* opt, int32_t n_frames) {
+  if (!opt || !opt->params || !opt->exp_avg || !opt->exp_avg_sq || !opt->shadow || opt->step < 1) return false;
+  if ((opt->loss_approx == nullptr) != (opt->frame_avg == nullptr)) return false;   // both or neither
+  if (opt->frame_avg_inline_n != 0 && (opt->frame_avg_inline_n != n_frames || opt->frame_avg_inline_n > ISDF_MAX_INLINE_FRAMES))
+    return false;
+  for (int f = 0; f < opt->frame_avg_inline_n; ++f)   // inline indices are host values: a negative one would write in front of frame_avg
+    if (opt->frame_avg_index_inline[f] < 0) return false;
+  return true;
+}
+
+// The optimiser's share of the step tail's block (opt: validated by optim_args_ok).  Returns the hyper-parameters for the launcher.
+static AdamwHyper tail_optim(TailParams& t, const isdf_optim_args& opt) {
+  t.params = opt.params; t.m = opt.exp_avg; t.v = opt.exp_avg_sq; t.shadow = (uint16_t*)opt.shadow;
+  t.grad_scale = opt.grad_scale;
+  FinalizeArgs& f = t.fin;
+  f.la_out = opt.loss_approx; f.fa_out = opt.frame_avg; f.fa_index = opt.frame_avg_index;
+  f.fa_inline_n = opt.frame_avg_inline_n;
+  for (int k = 0; k < opt.frame_avg_inline_n; ++k) f.fa_inline[k] = opt.frame_avg_index_inline[k];
+  return AdamwHyper{opt.lr, opt.beta1, opt.beta2, opt.eps, opt.weight_decay, opt.step};
+}
+
 static int train_step_impl(const isdf_net_cfg* net, const isdf_loss_cfg* loss, const float* params, const void* shadow,
                            const isdf_step_args* a, const isdf_step_out* o, void* workspace, int64_t workspace_bytes,
                            void* stream, const isdf_optim_args* opt) {
@@ -228,30 +200,26 @@ static int train_step_impl(const isdf_net_cfg* net, const isdf_loss_cfg* loss, c
   rc = launch_dw(d, st);
   if (rc) return rc;
   if (ev && hipEventRecord(ev[2], st) != hipSuccess) return ISDF_EHIP;
-  float* lossSums = o->reduce_buf + l.n_params;
-  float* blockLoss = lossSums + 8;
-  float* blockCnt = blockLoss + (int64_t)a->n_frames * 64;
-  float* extra = blockCnt + (int64_t)a->n_frames * 64;   // caller-owned tail (extra_floats), right behind isdf_reduce_floats
+  const ReduceLayout r = reduce_layout(l, a->n_frames);
+  TailParams t = {};
+  t.lay = l; t.dwPart = dwPart; t.vecPart = vecPart; t.vecStride = w.vecStride; t.grad = o->reduce_buf;
+  FinalizeArgs& f = t.fin;
+  f.wg_loss = wgLoss; f.maxTiles = w.nTiles; f.n_valid = a->n_valid; f.S = a->S; f.tot_ws = totLoss;
+  f.ib = a->indices_b; f.ih = a->indices_h; f.iw = a->indices_w; f.n_frames = a->n_frames; f.H = a->H; f.W = a->W;
+  f.loss_sums = o->reduce_buf + r.lossSums; f.block_loss = o->reduce_buf + r.blockLoss; f.block_cnt = o->reduce_buf + r.blockCnt;
+  f.mailbox = o->host_mailbox; f.extra = o->reduce_buf + r.extra;   // caller-owned tail (extra_floats), right behind isdf_reduce_floats
+  f.n_extra = a->extra_floats; f.extra_slot = a->extra_slot; f.extra_value = a->extra_value;
   if (opt) {   // single-GPU tail: slab reduction + AdamW + operand repack + loss/bin finalisation in one launch
-    rc = launch_step_tail(0, l, dwPart, vecPart, w.vecStride, o->reduce_buf, opt->params, opt->exp_avg, opt->exp_avg_sq,
-                          (uint16_t*)opt->shadow, opt->grad_scale, opt->lr, opt->beta1, opt->beta2, opt->eps,
-                          opt->weight_decay, opt->step, wgLoss, w.nTiles, a->n_valid, a->S, totLoss, a->indices_b,
-                          a->indices_h, a->indices_w, a->n_frames, a->H, a->W, lossSums, blockLoss, blockCnt,
-                          opt->loss_approx, opt->frame_avg, opt->frame_avg_index, st, o->host_mailbox, extra, a->extra_floats,
-                          a->extra_slot, a->extra_value, 0, opt->frame_avg_inline_n, opt->frame_avg_index_inline);
+    const AdamwHyper hyper = tail_optim(t, *opt);
+    rc = launch_step_tail(0, t, &hyper, 0, st);
     if (rc) return rc;
-    if (ev && hipEventRecord(ev[3], st) != hipSuccess) return ISDF_EHIP;
-    return ISDF_OK;
   }
   // two-call / data-parallel form: slab + partial reduction and loss/bin finalisation in ONE launch; the summed
   // gradient then goes to the all-reduce and isdf_adamw.  With o->split_event: TWO launches, the event between them -- the
   // message's suffix (layers from the cat layer up, out layer, loss sums, bins) is final at the event.
-  const int parts = o->split_event ? 2 : 1;
+  const int parts = opt ? 0 : o->split_event ? 2 : 1;   // (0: the fused tail above was the closing launch)
   for (int part = 1; part <= parts; ++part) {
-    rc = launch_step_tail(1, l, dwPart, vecPart, w.vecStride, o->reduce_buf, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f,
-                          0.f, 0.f, 0.f, 0.f, 1, wgLoss, w.nTiles, a->n_valid, a->S, totLoss, a->indices_b, a->indices_h,
-                          a->indices_w, a->n_frames, a->H, a->W, lossSums, blockLoss, blockCnt, nullptr, nullptr, nullptr,
-                          st, o->host_mailbox, extra, a->extra_floats, a->extra_slot, a->extra_value, parts == 1 ? 0 : part);
+    rc = launch_step_tail(1, t, nullptr, parts == 1 ? 0 : part, st);
     if (rc) return rc;
     if (parts == 2 && part == 1 && hipEventRecord((hipEvent_t)o->split_event, st) != hipSuccess) return ISDF_EHIP;
   }
@@ -268,12 +236,7 @@ int isdf_train_step(const isdf_net_cfg* net, const isdf_loss_cfg* loss, const fl
 int isdf_train_step_adamw(const isdf_net_cfg* net, const isdf_loss_cfg* loss, const isdf_step_args* a,
                           const isdf_step_out* o, const isdf_optim_args* opt, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-  if (!a || !opt || !opt->params || !opt->exp_avg || !opt->exp_avg_sq || !opt->shadow || opt->step < 1) return ISDF_EINVAL;
-  if ((opt->loss_approx == nullptr) != (opt->frame_avg == nullptr)) return ISDF_EINVAL;   // both or neither
-  if (opt->frame_avg_inline_n != 0 && (opt->frame_avg_inline_n != a->n_frames || opt->frame_avg_inline_n > ISDF_MAX_INLINE_FRAMES))
-    return ISDF_EINVAL;
-  for (int f = 0; f < opt->frame_avg_inline_n; ++f)   // inline indices are host values: a negative one would write in front of frame_avg
-    if (opt->frame_avg_index_inline[f] < 0) return ISDF_EINVAL;
+  if (!a || !optim_args_ok(opt, a->n_frames)) return ISDF_EINVAL;
   if (o && o->split_event) return ISDF_EINVAL;   // the fused form has no message to split
   return train_step_impl(net, loss, opt->params, opt->shadow, a, o, workspace, workspace_bytes, stream, opt);
 }
@@ -284,23 +247,20 @@ int isdf_train_step_finish(const isdf_net_cfg* net, const isdf_optim_args* opt, 
   NetLayout l; int rc = make_layout(net, &l);
   if (rc) return rc;
   if (!layout_supported(l)) return ISDF_EUNSUPPORTED;
-  if (!opt || !opt->params || !opt->exp_avg || !opt->exp_avg_sq || !opt->shadow || opt->step < 1 || !reduce_buf) return ISDF_EINVAL;
-  if ((opt->loss_approx == nullptr) != (opt->frame_avg == nullptr)) return ISDF_EINVAL;   // both or neither
+  if (!optim_args_ok(opt, n_frames) || !reduce_buf) return ISDF_EINVAL;
   if (opt->loss_approx && n_frames < 1) return ISDF_EINVAL;
-  if (opt->frame_avg_inline_n != 0 && (opt->frame_avg_inline_n != n_frames || opt->frame_avg_inline_n > ISDF_MAX_INLINE_FRAMES))
-    return ISDF_EINVAL;
-  for (int f = 0; f < opt->frame_avg_inline_n; ++f)
-    if (opt->frame_avg_index_inline[f] < 0) return ISDF_EINVAL;
   if (extra_floats < 0 || extra_floats > 1016 || n_frames < 0) return ISDF_EINVAL;
   if (extra_floats > 0 && !host_mailbox) return ISDF_EINVAL;   // the reduced tail has nowhere to go: say so instead of dropping it
-  const float* lossSums = reduce_buf + l.n_params;
-  const float* bl = lossSums + 8;
-  const int F = opt->loss_approx ? n_frames : 0;
-  return launch_adamw_pack(l, opt->params, opt->exp_avg, opt->exp_avg_sq, (uint16_t*)opt->shadow, reduce_buf,
-                           lossSums + ISDF_LS_COUNT, opt->grad_scale, opt->lr, opt->beta1, opt->beta2, opt->eps,
-                           opt->weight_decay, opt->step, (hipStream_t)stream, F, bl, bl + (int64_t)n_frames * 64,
-                           opt->loss_approx, opt->frame_avg, opt->frame_avg_index, lossSums, bl + (int64_t)n_frames * 128,
-                           extra_floats, host_mailbox, opt->frame_avg_inline_n, opt->frame_avg_index_inline);
+  const ReduceLayout r = reduce_layout(l, n_frames);
+  float* msg = const_cast<float*>(reduce_buf);   // phase 2 only reads the message
+  TailParams t = {};
+  t.lay = l; t.grad = msg; t.count_ptr = reduce_buf + r.lossSums + ISDF_LS_COUNT;
+  const AdamwHyper hyper = tail_optim(t, *opt);
+  FinalizeArgs& f = t.fin;
+  f.n_frames = opt->loss_approx ? n_frames : 0;
+  f.loss_sums = msg + r.lossSums; f.block_loss = msg + r.blockLoss; f.block_cnt = msg + r.blockCnt;
+  f.extra = msg + r.extra; f.n_extra = extra_floats; f.mailbox = host_mailbox;
+  return launch_adamw_pack(t, hyper, (hipStream_t)stream);
 }
 
 int isdf_allreduce_sum_f32(isdf_nccl_allreduce_fn nccl_all_reduce, void* comm, float* buf, int64_t count, void* stream) {
@@ -325,8 +285,8 @@ int isdf_frame_avg(const float* reduce_buf, int64_t n_params, int32_t n_frames, 
                    float* frame_avg_loss, const int32_t* frame_avg_index, void* stream) {
   isdf_clear_stale_hip_error();
   if (!reduce_buf || !loss_approx || !frame_avg_loss || n_frames < 1 || n_params < 0) return ISDF_EINVAL;
-  const float* bl = reduce_buf + n_params + 8;
-  return launch_frame_avg(bl, bl + (int64_t)n_frames * 64, n_frames, loss_approx, frame_avg_loss, frame_avg_index,
+  const ReduceLayout r = reduce_layout(n_params, n_frames);
+  return launch_frame_avg(reduce_buf + r.blockLoss, reduce_buf + r.blockCnt, n_frames, loss_approx, frame_avg_loss, frame_avg_index,
                           (hipStream_t)stream);
 }
 
@@ -354,11 +314,14 @@ int isdf_adamw(const isdf_net_cfg* net, float* params, float* exp_avg, float* ex
   NetLayout l; int rc = make_layout(net, &l);
   if (rc) return rc;
   if (!params || !exp_avg || !exp_avg_sq || !grad_sum || step < 1) return ISDF_EINVAL;
-  if (shadow && layout_supported(l))   // update + the four packed operand copies in one launch
-    return launch_adamw_pack(l, params, exp_avg, exp_avg_sq, (uint16_t*)shadow, grad_sum, count_ptr, grad_scale, lr,
-                             beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
-  rc = launch_adamw(params, exp_avg, exp_avg_sq, grad_sum, count_ptr, grad_scale, lr, beta1, beta2, eps, weight_decay,
-                    step, l.n_params, (hipStream_t)stream);
+  const AdamwHyper hyper = {lr, beta1, beta2, eps, weight_decay, step};
+  if (shadow && layout_supported(l)) {   // update + the four packed operand copies in one launch
+    TailParams t = {};
+    t.lay = l; t.grad = const_cast<float*>(grad_sum); t.count_ptr = count_ptr; t.grad_scale = grad_scale;
+    t.params = params; t.m = exp_avg; t.v = exp_avg_sq; t.shadow = (uint16_t*)shadow;
+    return launch_adamw_pack(t, hyper, (hipStream_t)stream);
+  }
+  rc = launch_adamw(params, exp_avg, exp_avg_sq, grad_sum, count_ptr, grad_scale, hyper, l.n_params, (hipStream_t)stream);
   if (rc || !shadow) return rc;
   return launch_pack(l, params, (uint16_t*)shadow, (hipStream_t)stream);
 }

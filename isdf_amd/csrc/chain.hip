@@ -22,6 +22,7 @@
 // register quad, so epilogues write 8-byte packed pieces back to the LDS tile.
 #include <atomic>
 #include "chain_dev.h"
+#include "launchers.h"
 
 namespace isdf {
 
@@ -1149,9 +1150,6 @@ static int launch_mode(const ChainParams& p, int64_t nTiles, hipStream_t st) {
   if (p.lay.HD == 256) return launch_oper<256, 512, MODE>(p, nTiles, st);   // realsense*.json: hidden 256, E = 381 / 465
   return launch_oper<512, 512, MODE>(p, nTiles, st);                         // BASELINE configs[4]
 }
-
-bool fwd_pair_supported(const NetLayout& l);                                        // fwd_pair.hip
-int launch_fwd_pair(const ChainParams& p, int64_t nTiles, hipStream_t st);
 
 // compute units of the device the launch goes to -- the STREAM's device, not the thread's current one (a caller may hold a stream of
 // another device); cached per ordinal in atomics (concurrent host threads).  256 on an unpartitioned MI355X.  Speed only: the

@@ -15,6 +15,7 @@
 // loads are in flight; the next stage's way into LDS rides behind the MFMAs of the
 // running one, slice by slice (dw_kernel's header).
 #include "isdf_common.h"
+#include "launchers.h"
 #include "chain_params.h"
 #include "chain_dev.h"
 

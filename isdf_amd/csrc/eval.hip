@@ -8,6 +8,7 @@
 // Both reductions are deterministic: per-block partial sums in double, combined in block order by one closing block; the
 // nearest neighbour is a minimum over integer keys (squared distance bits, then index), which no order can change.
 #include "isdf_common.h"
+#include "launchers.h"
 #include "gt_volume_dev.h"
 
 namespace isdf {

@@ -32,6 +32,7 @@
 // What bounds it: the SIMD issue port (0.88 utilised: a Softplus element is 38 issue cycles, a K = 256 stage has four per MFMA), not
 // the matrix pipe (0.50); packed fp32 instructions are no way around it (they occupy the matrix pipe), nor is wave priority.
 #include "chain_dev.h"
+#include "launchers.h"
 
 namespace isdf {
 

@@ -11,6 +11,7 @@
 // with the hardware-rate v_sqrt_f32 / v_rcp_f32 (1 ulp) it ships with -- the reference fixture
 // (99.9 % of the pixels within 1e-4) passes either way: profiles/r03_ingest_fastmath.txt.
 #include "isdf_common.h"
+#include "launchers.h"
 
 namespace isdf {
 

@@ -98,6 +98,15 @@ struct WorkspaceLayout {
   int64_t totalBytes;
 };
 
+// The reduction message (isdf_step_out.reduce_buf), in floats: [gradient sums n_params | 8 loss sums | block_loss F x 64 |
+// block_cnt F x 64 | caller-owned tail].  `total` = isdf_reduce_floats = what the kernels own; the tail starts right behind it.
+struct ReduceLayout { int64_t lossSums, blockLoss, blockCnt, extra, total; };
+inline ReduceLayout reduce_layout(int64_t n_params, int n_frames) {
+  const int64_t bl = n_params + 8, bins = (int64_t)n_frames * 64;
+  return ReduceLayout{n_params, bl, bl + bins, bl + 2 * bins, bl + 2 * bins};
+}
+inline ReduceLayout reduce_layout(const NetLayout& l, int n_frames) { return reduce_layout(l.n_params, n_frames); }
+
 // ---- launch status ------------------------------------------------------------
 // hipGetLastError() is sticky per host thread: an error left behind by ANOTHER library's HIP call (torch probes
 // produce benign ones) would otherwise be reported by our next launcher.  Entry points clear it first

@@ -1,0 +1,49 @@
+// Every host launcher and layout helper that crosses a translation unit, declared ONCE: the defining .hip file and capi.hip both
+// include this, so a definition that drifts from its declaration fails to compile instead of (at best) failing to link.
+#pragma once
+#include "isdf_common.h"
+
+namespace isdf {
+
+struct ChainParams; struct DwParams; struct TailParams; struct AdamwHyper;   // chain_params.h
+
+int launch_chain(const ChainParams& p, int mode, int64_t nTiles, hipStream_t st);                                   // chain.hip
+bool fwd_pair_supported(const NetLayout& l);                                                                        // fwd_pair.hip
+int launch_fwd_pair(const ChainParams& p, int64_t nTiles, hipStream_t st);
+int launch_dw(const DwParams& p, hipStream_t st);                                                                   // dw.hip
+int launch_sample_rays(const isdf_sample_args& a, const isdf_sample_out& o, void* scan_ws, hipStream_t st);         // sampler.hip
+int64_t sample_scan_bytes(int64_t max_rays);
+// optim.hip.  The step tail: `block` as capi.hip filled it; the launcher derives AdamwCoef and the grid.  phase 0 needs `hyper`,
+// phase 1 takes none; part 0 = one launch, 1 / 2 = the split tail (phase 1 only)
+int launch_step_tail(int phase, const TailParams& block, const AdamwHyper* hyper, int part, hipStream_t st);
+int launch_adamw_pack(const TailParams& block, const AdamwHyper& hyper, hipStream_t st);
+int launch_adamw(float* p, float* m, float* v, const float* g, const float* cnt, float gs, const AdamwHyper& hyper, int64_t n,
+                 hipStream_t st);
+int launch_pack(const NetLayout& L, const float* params, uint16_t* shadow, hipStream_t st);
+int launch_frame_avg(const float* bl, const float* bc, int F, float* la, float* fa, const int32_t* fa_index, hipStream_t st);
+int launch_bounds_pc(const int32_t* n_valid, int max_rays, int S, const float* pc, const float* z, const float* depth,
+                     const float* surf, int64_t n_surf, float* bounds, float* gv, hipStream_t st);
+int launch_normals(const float* depth, int H, int W, float fx, float fy, float cx, float cy, float* normals, hipStream_t st);   // ingest.hip
+int launch_render_depth(const int32_t* n_valid, int64_t n_host, int64_t max_rays, int S, const float* z, const float* sdf,
+                        const float* depth_sample, float th, float* view, int32_t* below, hipStream_t st);
+int64_t mesh_ws_layout(int64_t P, int64_t* nBlocks, int64_t* offOff, int64_t* offTot, int64_t* offVbase);          // mesh.hip
+int launch_marching_cubes(const float* vol, int32_t D0, int32_t D1, int32_t D2, float level, const float* A, const float* N,
+                          int64_t* counts, float* verts, float* normals, int64_t max_verts, int32_t* faces, int64_t max_faces,
+                          void* workspace, hipStream_t st);
+void mc_tables_host(int32_t* edge_corners, int8_t* tri_table);
+int launch_render_samples(const isdf_render_args& a, float* z, float* pc, hipStream_t st);                          // render.hip
+int launch_normal_points(const float* T_WC, const float* dirs_C, int64_t R, int64_t n_rays, const float* depth, float* pts,
+                         hipStream_t st);
+int launch_normal_finish(const float* T_WC, int64_t R, int64_t n_rays, const float* grad, float* normals, hipStream_t st);
+int launch_sdf_metrics(const isdf_gt_volume& vol, const float* pts, const float* sdf, int64_t n, int exclude_zero,  // eval.hip
+                       float oob_fill, double* record, float* gt_out, uint8_t* valid_out, double* part, hipStream_t st);
+int launch_region_metrics(const isdf_region_args& a, double* records, double* part, hipStream_t st);
+int launch_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
+                       double* dist_sum, unsigned long long* keys, double* part, hipStream_t st);
+int launch_slice_images(const isdf_colormap* cmap, const isdf_gt_volume* vol, const float* pts, const float* sdf, int64_t n,   // slices.hip
+                        float oob_fill, float chomp_eps, uint8_t* pred_rgb, float* gt_out, uint8_t* gt_rgb, float* pred_cost,
+                        float* gt_cost, hipStream_t st);
+int launch_plane_points(const float* origin, const float* du, const float* dv, int32_t H, int32_t W, float* pts_out,
+                        hipStream_t st);
+
+}  // namespace isdf

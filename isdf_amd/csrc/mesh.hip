@@ -12,6 +12,7 @@
 // the whole mesh fits the caller's buffers (they read the totals the scan left in the workspace), so no host round trip sits
 // between the passes.  Every workspace word is written before it is read in the same call: the workspace needs no zeroing.
 #include "isdf_common.h"
+#include "launchers.h"
 #include "mc_tables.h"
 
 namespace isdf {

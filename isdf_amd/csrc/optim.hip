@@ -5,11 +5,12 @@
 //   loss.bounds_pc                    isdf/modules/loss.py:56-89
 // All HBM-/latency-bound element-wise work: 16-B coalesced accesses, one pass.
 #include "isdf_common.h"
+#include "launchers.h"
+#include "chain_params.h"
 
 namespace isdf {
 
 // ---- AdamW (decoupled weight decay, bias-corrected) --------------------------
-struct AdamwCoef { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };
 __device__ __forceinline__ float adamw_update(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                               int64_t i, float gsum, float gs, const AdamwCoef& c) {
   // no FMA contraction: the stand-alone kernel and the fused step tail must round identically
@@ -115,17 +116,6 @@ __global__ void pack_kernel(NetLayout L, const float* __restrict__ P, uint16_t* 
 // ray is dropped if a later ray has its key, and the survivors are binned with
 // LDS atomics; each frame's 64 bins are then written once (no global atomics).
 constexpr int FIN_CAP = 12288;   // rays per frame staged in LDS (48 KB)
-struct FinalizeArgs {
-  const float* wg_loss; int64_t maxTiles; const int32_t* n_valid; int S; const float* tot_ws;
-  const int64_t *ib, *ih, *iw; int n_frames, H, W;
-  float *loss_sums, *block_loss, *block_cnt;
-  // optional (single-GPU tail only): the per-frame averages of loss.frame_avg written straight away --
-  // loss_approx [F,8,8] and frame_avg[fa_index ? fa_index[f] : f] (the keyframe store's frame_avg_losses)
-  float *la_out, *fa_out; const int32_t* fa_index;
-  int fa_inline_n; int32_t fa_inline[8];     // the same index list as kernel arguments (isdf_optim_args.frame_avg_index_inline)
-  // optional: loss sums mirrored into pinned host memory; caller-owned tail of the reduction message
-  float* mailbox; float* extra; int n_extra, extra_slot; float extra_value;
-};
 // binS: 32.32 fixed point -- integer LDS atomics are order-independent, so the bins (hence frame_avg_losses and
 // the keyframe-selection probabilities built from them) are bit-reproducible; float atomics are not
 struct FinalizeLds { float sh[16][8]; unsigned long long binS[64]; float binC[64]; int range[2]; int cnt[16][2]; uint32_t keys[FIN_CAP]; };
@@ -225,18 +215,6 @@ __device__ __forceinline__ void finalize_block(int block, const FinalizeArgs& a,
 // 347 us step) for world_size 1; the data-parallel path keeps them apart because the all-reduce of the
 // gradient sits between the reduction and the update.  Same summation order and AdamW arithmetic as the
 // separate kernels, so both paths produce bit-identical parameters.
-struct TailParams {
-  NetLayout lay;
-  const float* dwPart; const float* vecPart; int32_t vecStride;
-  float* grad;                       // [n_params] summed gradient (still written: reduce_buf contract)
-  float *params, *m, *v; uint16_t* shadow;
-  AdamwCoef c; float grad_scale;     // gradient = sum * grad_scale / (n_valid * S)   [PHASE 0]
-  const float* count_ptr;            // PHASE 2: gradient = grad[] * grad_scale / *count_ptr (reduced count)
-  FinalizeArgs fin;
-  int nW, nV;                        // blocks of the weight and the vector sections
-  int wBlock0;                       // first weight block of this launch (a split tail runs the weight section in two launches)
-};
-
 __device__ __forceinline__ void shadow_put(const NetLayout& L, uint16_t* sh, bool fwdSet, int64_t elem, float val,
                                            bool withResidual = false) {
   const uint32_t h = pack4<true>(val, 0.f, 0.f, 0.f).x & 0xffffu, b = pack4<false>(val, 0.f, 0.f, 0.f).x & 0xffffu;
@@ -444,9 +422,18 @@ __global__ __launch_bounds__(256) void bounds_pc_kernel(const int32_t* __restric
 }
 
 // ---- launchers -------------------------------------------------------------------
-int launch_adamw(float* p, float* m, float* v, const float* g, const float* cnt, float gs, float lr,
-                 float b1, float b2, float eps, float wd, int step, int64_t n, hipStream_t st) {
-  const AdamwCoef c = {lr, b1, b2, eps, wd, 1.f - powf(b1, (float)step), sqrtf(1.f - powf(b2, (float)step))};
+static AdamwCoef adamw_coef(const AdamwHyper& h) {
+  const float b1 = h.b1, b2 = h.b2; const int step = h.step;
+  return AdamwCoef{h.lr, b1, b2, h.eps, h.wd, 1.f - powf(b1, (float)step), sqrtf(1.f - powf(b2, (float)step))};
+}
+static void tail_sections(TailParams& p) {   // blocks of the weight and the vector sections
+  const int64_t total = (int64_t)dw_units(p.lay) * DW_BLK * DW_BLK;
+  p.nW = (int)((total + 1023) / 1024);
+  p.nV = (p.lay.L * p.lay.HD + p.lay.HD + 1 + 63) / 64;
+}
+int launch_adamw(float* p, float* m, float* v, const float* g, const float* cnt, float gs, const AdamwHyper& hyper, int64_t n,
+                 hipStream_t st) {
+  const AdamwCoef c = adamw_coef(hyper);
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, m, v, g, cnt, gs, c, n);
   return isdf_launch_status();
 }
@@ -455,41 +442,15 @@ int launch_pack(const NetLayout& L, const float* params, uint16_t* shadow, hipSt
   hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, L, params, shadow);
   return isdf_launch_status();
 }
-static FinalizeArgs finalize_args(const float* wg_loss, int64_t maxTiles, const int32_t* n_valid, int S, const float* tot_ws,
-                                  const int64_t* ib, const int64_t* ih, const int64_t* iw, int F, int H, int W,
-                                  float* loss_sums, float* bl, float* bc) {
-  FinalizeArgs a = {};
-  a.wg_loss = wg_loss; a.maxTiles = maxTiles; a.n_valid = n_valid; a.S = S; a.tot_ws = tot_ws; a.ib = ib; a.ih = ih; a.iw = iw;
-  a.n_frames = F; a.H = H; a.W = W; a.loss_sums = loss_sums; a.block_loss = bl; a.block_cnt = bc;
-  return a;
-}
-// phase 0: params/m/v/shadow + optim scalars + finalize args; phase 1: grad + finalize args only;
-// phase 2 (launch_adamw_pack): params/m/v/shadow + optim scalars + count_ptr, grad = reduced gradient
-int launch_step_tail(int phase, const NetLayout& L, const float* dwPart, const float* vecPart, int vecStride, float* grad,
-                     float* params, float* m, float* v, uint16_t* shadow, float grad_scale, float lr, float b1, float b2,
-                     float eps, float wd, int step, const float* wg_loss, int64_t maxTiles, const int32_t* n_valid, int S,
-                     const float* tot_ws, const int64_t* ib, const int64_t* ih, const int64_t* iw, int F, int H, int W,
-                     float* loss_sums, float* bl, float* bc, float* la_out, float* fa_out, const int32_t* fa_index,
-                     hipStream_t st, float* mailbox, float* extra, int n_extra, int extra_slot, float extra_value, int part,
-                     int fa_inline_n, const int32_t* fa_inline) {
+int launch_step_tail(int phase, const TailParams& block, const AdamwHyper* hyper, int part, hipStream_t st) {
   // part 0: everything in one launch.  Split tail (phase 1 only): part 1 = weight blocks of the dW units from the cat layer up +
   // vector section + finalisation (the message's suffix, isdf_reduce_split_floats), part 2 = the weight blocks below.
-  TailParams p = {};
-  p.lay = L; p.dwPart = dwPart; p.vecPart = vecPart; p.vecStride = vecStride; p.grad = grad;
-  p.params = params; p.m = m; p.v = v; p.shadow = shadow; p.grad_scale = grad_scale;
-  if (phase == 0)
-    p.c = AdamwCoef{lr, b1, b2, eps, wd, 1.f - powf(b1, (float)step), sqrtf(1.f - powf(b2, (float)step))};
-  p.fin = finalize_args(wg_loss, maxTiles, n_valid, S, tot_ws, ib, ih, iw, F, H, W, loss_sums, bl, bc);
-  if (la_out && fa_out) {
-    p.fin.la_out = la_out; p.fin.fa_out = fa_out; p.fin.fa_index = fa_index;
-    p.fin.fa_inline_n = fa_inline_n;
-    for (int k = 0; k < fa_inline_n && k < 8; ++k) p.fin.fa_inline[k] = fa_inline[k];
-  }
-  p.fin.mailbox = mailbox; p.fin.extra = extra; p.fin.n_extra = n_extra; p.fin.extra_slot = extra_slot; p.fin.extra_value = extra_value;
-  const int64_t total = (int64_t)dw_units(L) * DW_BLK * DW_BLK;
-  p.nW = (int)((total + 1023) / 1024);
-  p.nV = (L.L * L.HD + L.HD + 1 + 63) / 64;
-  int tailBlocks = p.nV + 1 + F;
+  if ((phase != 0 && phase != 1) || (phase == 0 && !hyper)) return ISDF_EINVAL;
+  TailParams p = block;
+  const NetLayout& L = p.lay;
+  if (phase == 0) p.c = adamw_coef(*hyper);
+  tail_sections(p);
+  int tailBlocks = p.nV + 1 + p.fin.n_frames;
   if (part != 0) {
     if (phase != 1) return ISDF_EINVAL;
     int unitsBelow = 0;                     // dW units of the layers below the cat layer (units are numbered layer by layer)
@@ -504,28 +465,13 @@ int launch_step_tail(int phase, const NetLayout& L, const float* dwPart, const f
   else hipLaunchKernelGGL(step_tail_kernel<1>, grid, dim3(1024), 0, st, p);
   return isdf_launch_status();
 }
-// n_frames > 0: the same launch also turns the (all-reduced) bins into loss_approx / frame averages (the data-parallel
-// step's closing launch, isdf_train_step_finish)
-int launch_adamw_pack(const NetLayout& L, float* params, float* m, float* v, uint16_t* shadow, const float* grad,
-                      const float* count_ptr, float grad_scale, float lr, float b1, float b2, float eps, float wd,
-                      int step, hipStream_t st, int n_frames = 0, const float* bl = nullptr, const float* bc = nullptr,
-                      float* la = nullptr, float* fa = nullptr, const int32_t* fa_index = nullptr,
-                      const float* loss_sums = nullptr, const float* extra = nullptr, int n_extra = 0, float* mailbox = nullptr,
-                      int fa_inline_n = 0, const int32_t* fa_inline = nullptr) {
-  TailParams p = {};
-  p.fin.fa_inline_n = fa_inline_n;
-  for (int k = 0; k < fa_inline_n && k < 8; ++k) p.fin.fa_inline[k] = fa_inline[k];
-  p.fin.block_loss = const_cast<float*>(bl); p.fin.block_cnt = const_cast<float*>(bc);
-  p.fin.la_out = la; p.fin.fa_out = fa; p.fin.fa_index = fa_index; p.fin.n_frames = n_frames;
-  p.fin.loss_sums = const_cast<float*>(loss_sums); p.fin.extra = const_cast<float*>(extra); p.fin.n_extra = n_extra;
-  p.fin.mailbox = mailbox;
-  p.lay = L; p.grad = const_cast<float*>(grad); p.params = params; p.m = m; p.v = v; p.shadow = shadow;
-  p.grad_scale = grad_scale; p.count_ptr = count_ptr;
-  p.c = AdamwCoef{lr, b1, b2, eps, wd, 1.f - powf(b1, (float)step), sqrtf(1.f - powf(b2, (float)step))};
-  const int64_t total = (int64_t)dw_units(L) * DW_BLK * DW_BLK;
-  p.nW = (int)((total + 1023) / 1024);
-  p.nV = (L.L * L.HD + L.HD + 1 + 63) / 64;
-  hipLaunchKernelGGL(step_tail_kernel<2>, dim3((unsigned)(p.nW + p.nV + n_frames + (mailbox ? 1 : 0))), dim3(1024), 0, st, p);
+// fin.n_frames > 0: the same launch also turns the (all-reduced) bins into loss_approx / frame averages; fin.mailbox: one more
+// block mirrors the reduced loss sums and tail to the host (the data-parallel step's closing launch, isdf_train_step_finish)
+int launch_adamw_pack(const TailParams& block, const AdamwHyper& hyper, hipStream_t st) {
+  TailParams p = block;
+  p.c = adamw_coef(hyper);
+  tail_sections(p);
+  hipLaunchKernelGGL(step_tail_kernel<2>, dim3((unsigned)(p.nW + p.nV + p.fin.n_frames + (p.fin.mailbox ? 1 : 0))), dim3(1024), 0, st, p);
   return isdf_launch_status();
 }
 int launch_frame_avg(const float* bl, const float* bc, int F, float* la, float* fa, const int32_t* fa_index,

@@ -10,6 +10,7 @@
 // Arithmetic is the reference's, operation by operation; the file is built with -ffp-contract=off (build.py), so no
 // multiply-add is fused.
 #include "isdf_common.h"
+#include "launchers.h"
 
 namespace isdf {
 

@@ -22,6 +22,7 @@
 // (4-B / 12-B per lane), which is where 86 % of the bytes go (432 of 500 B per ray), and in Philox mode ONE
 // Philox4x32-10 call per lane feeds its four points (7.75 calls per ray instead of 28).
 #include "isdf_common.h"
+#include "launchers.h"
 
 namespace isdf {
 

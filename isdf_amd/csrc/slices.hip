@@ -6,6 +6,7 @@
 // and the points of a plane (isdf_plane_points).  Built with -ffp-contract=off (build.py): every operation below is rounded to
 // fp32 on its own, so numpy float32 models (tests/slice_model.py) equal the colour index, the cost and the points bit for bit.
 #include "isdf_common.h"
+#include "launchers.h"
 #include "gt_volume_dev.h"
 
 namespace isdf {

@@ -18,6 +18,7 @@ from . import _ffi
 
 N_DIRS = 21
 FWD_OPERANDS = ("bf16", "fp16", "fp16x2", "fp16x2_full")   # isdf_net_cfg.fwd_operand = index
+ADAMW_LR, ADAMW_WEIGHT_DECAY, ADAMW_BETAS, ADAMW_EPS = 0.0013, 0.012, (0.9, 0.999), 1e-8   # what an `optim` dict leaves out
 
 
 @dataclass
@@ -412,20 +413,8 @@ class Engine:
                 a.extra_slot, a.extra_value = int(extra_slot), float(extra_value)
                 o.prof_events = prof_events          # (bench.py: four hipEvent_t around the step's kernels on some steps; None otherwise)
                 if q is not None:
-                    self.opt_step += 1
-                    betas = optim.get("betas", (0.9, 0.999))
-                    q.lr, q.weight_decay = float(optim.get("lr", 0.0013)), float(optim.get("weight_decay", 0.012))
-                    q.beta1, q.beta2, q.eps = float(betas[0]), float(betas[1]), float(optim.get("eps", 1e-8))
-                    q.grad_scale, q.step = float(optim.get("grad_scale", 1.0)), int(self.opt_step)
-                    if fi_inline:
-                        q.frame_avg_index_inline[:F] = fi
-                    _ffi.check(self.lib.isdf_train_step_adamw(C.byref(self.cnet), C.byref(closs), C.byref(a), C.byref(o),
-                                                              C.byref(q), self._ws_ptr, ws.numel(), _stream(self.device)),
-                               "isdf_train_step_adamw")
-                else:
-                    _ffi.check(self.lib.isdf_train_step(C.byref(self.cnet), C.byref(closs), self._params_ptr, self._shadow_ptr,
-                                                        C.byref(a), C.byref(o), self._ws_ptr, ws.numel(), _stream(self.device)),
-                               "isdf_train_step")
+                    self._step_scalars(q, optim, F, fi if fi_inline else None)
+                self._launch_step(closs, a, o, q, ws)
                 return dict(dbg)      # a fresh dict per call; its `loss_approx` tensor is the plan's reused buffer (overwritten by
                                       # the next step on this buffer set, two steps later)
         # [isdf_reduce_floats | reduce_extra caller-owned floats]: the kernels write the first part; the tail belongs to the
@@ -491,33 +480,43 @@ class Engine:
                                                  dbg["tot_loss_mat"].data_ptr())
             if lc.bounds_method == "pc":
                 dbg["pc_bounds"], dbg["pc_grad_vec"] = keep[-2].view(R0, S), keep[-1].view(R0, S, 3)
-        if optim is not None:
-            q = self._optim_args(optim, F, dbg, keep)
-            _ffi.check(self.lib.isdf_train_step_adamw(C.byref(self.cnet), C.byref(closs), C.byref(a), C.byref(o),
-                                                      C.byref(q), _ffi.ptr(ws), ws.numel(), _stream(self.device)),
-                       "isdf_train_step_adamw")
-        else:
-            _ffi.check(self.lib.isdf_train_step(C.byref(self.cnet), C.byref(closs), _ffi.ptr(self.params),
-                                                _ffi.ptr(self.shadow), C.byref(a), C.byref(o), _ffi.ptr(ws),
-                                                ws.numel(), _stream(self.device)), "isdf_train_step")
+        q = None if optim is None else self._optim_args(optim, F, dbg, keep)
+        self._launch_step(closs, a, o, q, ws)
         dbg["_keep"] = keep
         if plan_key is not None:
             # re-key with the buffers this call may have (re)allocated
             plan_key = plan_key[:-2] + (self.reduce_buf.data_ptr(), self._ws.data_ptr())
-            self._step_plans[smp["_slot"]] = (plan_key, closs, a, o, q if optim is not None else None, ws, dbg)
+            self._step_plans[smp["_slot"]] = (plan_key, closs, a, o, q, ws, dbg)
         return dbg
+
+    def _launch_step(self, closs, a, o, q, ws):
+        """isdf_train_step_adamw with the isdf_optim_args `q`, isdf_train_step with q None, on the buffers train_step last set up"""
+        if q is not None:
+            _ffi.check(self.lib.isdf_train_step_adamw(C.byref(self.cnet), C.byref(closs), C.byref(a), C.byref(o),
+                                                      C.byref(q), self._ws_ptr, ws.numel(), _stream(self.device)),
+                       "isdf_train_step_adamw")
+        else:
+            _ffi.check(self.lib.isdf_train_step(C.byref(self.cnet), C.byref(closs), self._params_ptr, self._shadow_ptr,
+                                                C.byref(a), C.byref(o), self._ws_ptr, ws.numel(), _stream(self.device)),
+                       "isdf_train_step")
+
+    def _step_scalars(self, q, optim, F, inline_idx=None):
+        """advances the optimiser step; writes lr .. step and, window inline, its F frame-average indices (Python ints) into `q`"""
+        self.opt_step += 1
+        betas = optim.get("betas", ADAMW_BETAS)
+        q.lr, q.weight_decay = float(optim.get("lr", ADAMW_LR)), float(optim.get("weight_decay", ADAMW_WEIGHT_DECAY))
+        q.beta1, q.beta2, q.eps = float(betas[0]), float(betas[1]), float(optim.get("eps", ADAMW_EPS))
+        q.grad_scale, q.step = float(optim.get("grad_scale", 1.0)), int(self.opt_step)
+        if inline_idx is not None:
+            q.frame_avg_index_inline[:F] = inline_idx
 
     def _optim_args(self, optim, F, dbg, keep):
         """isdf_optim_args of this engine's buffers; advances the optimiser step.  optim: dict(lr, weight_decay, betas,
         eps, grad_scale[, frame_avg_out, frame_avg_index])"""
-        self.opt_step += 1
-        betas = optim.get("betas", (0.9, 0.999))
         q = _ffi.OptimArgs()
         q.params, q.exp_avg, q.exp_avg_sq = self.params.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
         q.shadow = self.shadow.data_ptr()
-        q.lr, q.weight_decay = float(optim.get("lr", 0.0013)), float(optim.get("weight_decay", 0.012))
-        q.beta1, q.beta2, q.eps = float(betas[0]), float(betas[1]), float(optim.get("eps", 1e-8))
-        q.grad_scale, q.step = float(optim.get("grad_scale", 1.0)), int(self.opt_step)
+        inline_idx = None
         if optim.get("frame_avg_out") is not None:   # loss.frame_avg fused into the same launch
             la = torch.empty(F, 8, 8, dtype=torch.float32, device=self.device)
             fa_out, fa_idx = optim["frame_avg_out"], optim.get("frame_avg_index")
@@ -526,12 +525,13 @@ class Engine:
             if isinstance(fa_idx, (tuple, list)):     # the window as kernel arguments (isdf_optim_args.frame_avg_index_inline)
                 assert len(fa_idx) == F <= _ffi.MAX_INLINE_FRAMES
                 q.frame_avg_inline_n = F
-                q.frame_avg_index_inline[:F] = [int(v) for v in fa_idx]
+                inline_idx = [int(v) for v in fa_idx]
             else:
                 assert fa_idx is None or (fa_idx.dtype == torch.int32 and fa_idx.numel() == F)
                 q.frame_avg_index = None if fa_idx is None else fa_idx.data_ptr()
             dbg["loss_approx"] = la
             keep += [fa_out, fa_idx]
+        self._step_scalars(q, optim, F, inline_idx)
         return q
 
     def allreduce_direct(self, rccl):
@@ -552,16 +552,9 @@ class Engine:
         plan = self._step_plans.get("finish")
         if plan is not None and plan[0] == fkey:      # same buffers as the last call: reuse the struct, bump the scalars
             _, q, dbg = plan
-            self.opt_step += 1
-            betas = optim.get("betas", (0.9, 0.999))
-            q.lr, q.weight_decay = float(optim.get("lr", 0.0013)), float(optim.get("weight_decay", 0.012))
-            q.beta1, q.beta2, q.eps = float(betas[0]), float(betas[1]), float(optim.get("eps", 1e-8))
-            q.grad_scale, q.step = float(optim.get("grad_scale", 1.0)), int(self.opt_step)
-            if fi_inline:
-                q.frame_avg_index_inline[:n_frames] = fi
+            self._step_scalars(q, optim, n_frames, fi if fi_inline else None)
         else:
             q = self._optim_args(optim, n_frames, dbg, keep)
-            dbg["_keep"] = keep
             self._step_plans["finish"] = (fkey, q, dbg)
         _ffi.check(self.lib.isdf_train_step_finish(C.byref(self.cnet), C.byref(q), _ffi.ptr(self.reduce_buf), int(n_frames),
                                                    int(self.reduce_extra), _ffi.ptr(self.mailbox), _stream(self.device)),
@@ -788,7 +781,7 @@ class Engine:
         return pts
 
     # ---- AdamW ----------------------------------------------------------------------
-    def adamw(self, lr=0.0013, weight_decay=0.012, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0,
+    def adamw(self, lr=ADAMW_LR, weight_decay=ADAMW_WEIGHT_DECAY, betas=ADAMW_BETAS, eps=ADAMW_EPS, grad_scale=1.0,
               use_device_count=True):
         """torch.optim.AdamW.step on the flat buffer (trainer.py:435-439,982); the
         summed gradient is divided by the (all-reduced) element count on device."""

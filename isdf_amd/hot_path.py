@@ -290,6 +290,11 @@ class HotPath:
         sc = self._sample_cfg(n_strat=S - self.n_surf_samples)
         return s, sc
 
+    def _optim_kw(self, **extra):
+        """the engine's `optim` dict from the optimiser's (only) parameter group, plus `extra`"""
+        g = self.optimiser.param_groups[0]
+        return dict(lr=g["lr"], weight_decay=g["weight_decay"], betas=g["betas"], eps=g["eps"], **extra)
+
     def _step_kernels(self, s, sc, fused_optim, frame_avg_dst):
         """sampler outputs -> reduce buffer (+ optimiser when fused).  Returns (loss_approx, frame_avg_loss)."""
         hip, eng = self._hip, self.engine
@@ -303,8 +308,7 @@ class HotPath:
                 kw = dict(noise_std=self.noise_std, noise_seed=dp.rank_seed(hip.seed, self._rank()),
                           noise_offset=hip.noise_count)
         if fused_optim:
-            g = self.optimiser.param_groups[0]
-            kw["optim"] = dict(lr=g["lr"], weight_decay=g["weight_decay"], betas=g["betas"], eps=g["eps"])
+            kw["optim"] = self._optim_kw()
             if frame_avg_dst is not None:   # frames.frame_avg_losses[idxs] = ... inside the launch
                 kw["optim"].update(frame_avg_out=frame_avg_dst[0], frame_avg_index=frame_avg_dst[1])
         if hip.dist_group is not None and self.bounds_method == "pc":
@@ -434,9 +438,7 @@ class HotPath:
         if not fused and direct and hip.fuse_optimiser:
             # two-call / data-parallel form: ONE closing launch = AdamW on the (all-reduced) gradient sums + operand
             # repack + `frames.frame_avg_losses[idxs] = frame_avg_loss` from the reduced bins (trainer.py:979-982)
-            g = self.optimiser.param_groups[0]
-            eng.train_step_finish(len(idxs), dict(lr=g["lr"], weight_decay=g["weight_decay"], betas=g["betas"], eps=g["eps"],
-                                                  frame_avg_out=fal, frame_avg_index=fidx))
+            eng.train_step_finish(len(idxs), self._optim_kw(frame_avg_out=fal, frame_avg_index=fidx))
         else:
             if not fused or not direct:                # separate launches (caller-owned frame_avg_losses layout, or
                 if direct:                             # fuse_optimiser=False: the reference's call sequence)
