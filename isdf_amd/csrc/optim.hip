@@ -387,6 +387,11 @@ __global__ __launch_bounds__(256) void bounds_pc_kernel(const int32_t* __restric
                                                         const float* __restrict__ depth, const float* __restrict__ surf,
                                                         int64_t n_surf, float* __restrict__ bounds,
                                                         float* __restrict__ grad_vec) {
+  // no FMA contraction: the squared distance is the five roundings it is written as, the same on every rank and in
+  // tests/loss_model.py's fp32 model (bounds bit for bit, ties by index).  The pragma and plain operators, not __fmul_rn /
+  // __fadd_rn: those are inline functions holding a plain product and sum compiled under the file's contraction mode, and once
+  // inlined they were fused all the same (fma(dx, dx, dy dy) + dz dz)
+#pragma clang fp contract(off)
   __shared__ float sx[256], sy[256], sz[256];
   const int64_t Rl = *n_valid, P = Rl * S;
   const int64_t R = surf ? n_surf : Rl;                  // size of the surface set
@@ -405,7 +410,7 @@ __global__ __launch_bounds__(256) void bounds_pc_kernel(const int32_t* __restric
     const int cnt = (int)((R - r0) < 256 ? (R - r0) : 256);
     for (int k = 0; k < cnt; ++k) {
       const float dx = px - sx[k], dy = py - sy[k], dz = pz - sz[k];
-      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+      const float d2 = (dx * dx + dy * dy) + dz * dz;
       if (d2 < best) { best = d2; bi = r0 + k; }
     }
   }

@@ -22,6 +22,7 @@ import torch
 import oracle.isdf_oracle as orc
 from tests import golden_util as gu
 from tests import spill_model as sm
+from tests.gpu_step_util import pe_aux as _pe_aux, smp as _smp
 
 pytestmark = pytest.mark.gpu
 
@@ -145,15 +146,6 @@ def _batch(g, R, S, prefix=""):
     return {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in b.items()}
 
 
-def _smp(b):
-    d = lambda a: torch.as_tensor(a).cuda()
-    R, S = b["z_vals"].shape
-    return dict(n_valid=torch.tensor([R], dtype=torch.int32, device="cuda"), pc=d(b["pc"]), z_vals=d(b["z_vals"]),
-                depth_sample=d(b["depth_sample"]), dirs_C_sample=d(b["dirs_C_sample"]), dirs_W_sample=d(b["dirs_W_sample"]),
-                norm_sample=None if b["norm_sample"] is None else d(b["norm_sample"]), indices_b=d(b["indices_b"]),
-                indices_h=d(b["indices_h"]), indices_w=d(b["indices_w"]), max_rays=R, S=S, n_frames=b["n_frames"])
-
-
 def _step(eng, b, lc, sc):
     """one training step -> dict of float64 host arrays: grads (sums / N), sdf, sdf_grad, tot_loss_mat, loss sums, bins, raw buffer"""
     dbg = eng.train_step(_smp(b), lc, sc, noise=torch.as_tensor(b["noise"]).cuda(), debug=True)
@@ -175,16 +167,6 @@ def _slices(fix):
         out[k] = (off, shp)
         off += int(np.prod(shp))
     return out
-
-
-def _pe_aux(eng, N):
-    """the chain kernel's per-point record for the dW kernel, read back from the workspace: [x' (3), 0, gbar' (3), s_G] ([N, 8]).
-    Offset as make_workspace (isdf_common.h) lays it out: the last region before the 256 + 4 096 spare bytes."""
-    import ctypes as C
-    total = int(eng.lib.isdf_workspace_bytes(C.byref(eng.cnet), N, 1))
-    nbytes = -(-N // 64) * 64 * 32
-    off = total - 256 - 4096 - nbytes
-    return eng._ws[off:off + nbytes].view(torch.float32).view(-1, 8)[:N].cpu().numpy().astype(np.float64)
 
 
 def _check_gb_scale(eng, N, nf, terms):
