@@ -178,6 +178,24 @@ class pinned_stream:
             _PINNED[self.idx] = self.prev
 
 
+def to_host(*tensors):
+    """device tensors of any dtype -> numpy arrays, through ONE copy (None stays None)"""
+    order = sorted((k for k, t in enumerate(tensors) if t is not None), key=lambda k: -tensors[k].element_size())
+    out = [None] * len(tensors)
+    if not order:
+        return out
+    # widest elements first: every array then starts at a multiple of its element size
+    flat = torch.cat([tensors[k].contiguous().reshape(-1).view(torch.uint8) for k in order]).cpu().numpy()
+    off = 0
+    for k in order:
+        t = tensors[k]
+        nb = t.numel() * t.element_size()
+        dt = np.dtype(str(t.dtype).replace("torch.", ""))
+        out[k] = flat[off:off + nb].view(dt).reshape(tuple(t.shape))
+        off += nb
+    return out
+
+
 class Engine:
     def __init__(self, net: NetConfig, device="cuda"):
         self.lib = _ffi.lib()
@@ -200,6 +218,10 @@ class Engine:
         self._ws = None
         self._ws_key = None
         self._scan_ws = None      # sampler look-back state (zero on first use, self re-arming afterwards)
+        self._scan_ptr = None     # ... and its address as the launches take it
+        self._smp_ring = None     # [key, two sampler buffer sets, current slot, their two call plans] of sample(reuse=True)
+        self._ws_ptr = self._params_ptr = self._shadow_ptr = None    # addresses train_step last set up for _launch_step
+        self._fa_index_cache = {}     # host-side window -> its int32 device tensor (frame_avg)
         self._mesher = None       # marching-cubes workspace, count pair and output capacity (isdf_amd.mesh.Mesher)
         self._renderer = None     # rendered-view workspace (isdf_amd.render.Renderer)
         self._eval_ws = None      # partial records of isdf_sdf_metrics
@@ -265,7 +287,7 @@ class Engine:
         key = (R0, S, bool(want_T), normal_batch is not None)
         slot = None
         if reuse:   # the step loop's fast path: ten torch.empty calls sit in front of the first launch otherwise.
-            ring = getattr(self, "_smp_ring", None)      # TWO alternating buffer sets: the previous step's outputs
+            ring = self._smp_ring                        # TWO alternating buffer sets: the previous step's outputs
             if ring is None or ring[0] != key:           # (trainer.active_pixels) stay intact for one more step
                 ring = self._smp_ring = [key, [None, None], 0, [None, None]]
                 # the cached step plans hold raw pointers into the buffer sets just dropped: a later ring of the same shape may
@@ -338,7 +360,7 @@ class Engine:
         need = int(self.lib.isdf_sample_scan_bytes(R0))
         if self._scan_ws is None or self._scan_ws.numel() < need:
             self._scan_ws = torch.zeros(max(need, 4096), dtype=torch.uint8, device=dev)
-            if getattr(self, "_smp_ring", None) is not None:
+            if self._smp_ring is not None:
                 self._smp_ring[3] = [None, None]
         self._scan_ptr = _ffi.ptr(self._scan_ws)
         _ffi.check(self.lib.isdf_sample_rays(C.byref(a), C.byref(o), self._scan_ptr, self._scan_ws.numel(),
@@ -575,7 +597,7 @@ class Engine:
         A tuple / list index (the host-side window) is converted once per distinct window and cached."""
         if isinstance(index, (tuple, list)):
             key = tuple(int(v) for v in index)
-            cache = self.__dict__.setdefault("_fa_index_cache", {})
+            cache = self._fa_index_cache
             if key not in cache:
                 if len(cache) > 64:
                     cache.clear()
@@ -632,19 +654,26 @@ class Engine:
         return self._renderer(T_WC, dirs_C, H, W, n_samples, **kw)
 
     # ---- evaluation against ground truth -----------------------------------------------
+    def _flat(self, t, dtype, width=None):
+        """`t` on this engine's device as contiguous `dtype`, flat or (width given) as rows of `width`"""
+        t = t.detach().reshape(-1) if width is None else t.detach().reshape(-1, width)
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _check_volume(self, name, volume):
+        vd = volume.values.device
+        if vd.type != self.device.type or (self.device.index is not None and vd.index != self.device.index):
+            raise ValueError("%s: the ground-truth volume is on %s, the engine on %s" % (name, vd, self.device))
+
     def sdf_metrics(self, volume, pts, sdf, exclude_zero_gt=True, per_point=False, oob_fill=0.0):
         """(record f64[24], gt [n] or None, valid u8[n] or None) on the device: isdf_sdf_metrics, the ground-truth lookup and
         every sum of Trainer.eval_sdf / eval_object_sdf / eval_traj_cost (trainer.py:1831-1866,1993-2003,2026-2050) in one
         pass.  `volume`: isdf_amd.metrics.GtVolume; pts [n,3], sdf [n].  No host synchronisation; isdf_amd.metrics.sdf_metrics
         copies the record once and names its fields."""
-        p = pts.detach().reshape(-1, 3).to(device=self.device, dtype=torch.float32).contiguous()
-        s = sdf.detach().reshape(-1).to(device=self.device, dtype=torch.float32).contiguous()
+        p, s = self._flat(pts, torch.float32, 3), self._flat(sdf, torch.float32)
         n = int(p.shape[0])
         if s.numel() != n:
             raise ValueError("sdf_metrics: %d points but %d sdf values" % (n, s.numel()))
-        vd = volume.values.device
-        if vd.type != self.device.type or (self.device.index is not None and vd.index != self.device.index):
-            raise ValueError("sdf_metrics: the ground-truth volume is on %s, the engine on %s" % (volume.values.device, self.device))
+        self._check_volume("sdf_metrics", volume)
         if self._eval_ws is None:
             self._eval_ws = torch.empty(_ffi.SDF_METRICS_WS_BYTES, dtype=torch.uint8, device=self.device)
         record = torch.empty(_ffi.METRICS_RECORD, dtype=torch.float64, device=self.device)
@@ -663,8 +692,7 @@ class Engine:
         in both sdf sets); sdf_grad [n,3]: the gradient sets named by flag bits 4 / 8 are evaluated.  out: a [2, 27] float64 view
         to write into (several legs, one copy).  No host synchronisation."""
         dev = self.device
-        p = pts.detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
-        s = sdf.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        p, s = self._flat(pts, torch.float32, 3), self._flat(sdf, torch.float32)
         n = int(p.shape[0])
         if s.numel() != n:
             raise ValueError("region_metrics: %d points but %d sdf values" % (n, s.numel()))
@@ -673,23 +701,21 @@ class Engine:
         a = _ffi.RegionArgs()
         keep = [p, s]
         if volume is not None:
-            vd = volume.values.device
-            if vd.type != dev.type or (dev.index is not None and vd.index != dev.index):
-                raise ValueError("region_metrics: the ground-truth volume is on %s, the engine on %s" % (vd, dev))
+            self._check_volume("region_metrics", volume)
             vc = volume.to_c()
             keep.append(vc)
             a.vol = C.pointer(vc)
             for k in range(3):
                 a.spacing[k], a.origin[k] = volume.spacing[k], volume.origin[k]
         else:
-            g = gt.detach().reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+            g = self._flat(gt, torch.float64)
             if g.numel() != n:
                 raise ValueError("region_metrics: %d points but %d ground-truth values" % (n, g.numel()))
             keep.append(g)
             a.gt_in = g.data_ptr() if n else 8        # n = 0: an empty tensor has no address; nothing is read
         for name, t, dt, width in (("sdf_grad", sdf_grad, torch.float32, 3), ("flags", flags, torch.uint8, 1)):
             if t is not None:
-                t = t.detach().reshape(-1).to(device=dev, dtype=dt).contiguous()
+                t = self._flat(t, dt)
                 if t.numel() != n * width:
                     raise ValueError("region_metrics: %s has %d elements for %d points" % (name, t.numel(), n))
                 keep.append(t)
@@ -710,8 +736,7 @@ class Engine:
         """(dist [n] f32, index [n] i32 or None, dist_sum f64[1]) on the device: isdf_nn_distance, the exact distance from every
         query point to its nearest target point (the KD-tree queries of metrics.accuracy / completion, metrics.py:48-59) by
         brute force; the lowest target index on ties.  No host synchronisation."""
-        q = query.detach().reshape(-1, 3).to(device=self.device, dtype=torch.float32).contiguous()
-        t = target.detach().reshape(-1, 3).to(device=self.device, dtype=torch.float32).contiguous()
+        q, t = self._flat(query, torch.float32, 3), self._flat(target, torch.float32, 3)
         n, m = int(q.shape[0]), int(t.shape[0])
         if n > 0 and m < 1:
             raise ValueError("nn_distance: empty target set")
@@ -733,8 +758,8 @@ class Engine:
         (trainer.py:1593-1639,1796-1807,1453-1461) in one pass.  sdf [n] (or None: no predicted outputs), pts [n,3] (needed with
         `volume`); cmap: isdf_amd.slices.Colormap (or None: no colours); volume: isdf_amd.metrics.GtVolume (or None: no ground
         truth); chomp_eps: epsilon of the CHOMP cost fields (or None).  No host synchronisation."""
-        s = None if sdf is None else sdf.detach().reshape(-1).to(device=self.device, dtype=torch.float32).contiguous()
-        p = None if pts is None else pts.detach().reshape(-1, 3).to(device=self.device, dtype=torch.float32).contiguous()
+        s = None if sdf is None else self._flat(sdf, torch.float32)
+        p = None if pts is None else self._flat(pts, torch.float32, 3)
         if s is None and p is None:
             raise ValueError("slice_images: neither sdf nor pts")
         n = int(s.numel() if s is not None else p.shape[0])
@@ -743,9 +768,7 @@ class Engine:
         if volume is not None:
             if p is None:
                 raise ValueError("slice_images: the ground truth needs the points")
-            vd = volume.values.device
-            if vd.type != self.device.type or (self.device.index is not None and vd.index != self.device.index):
-                raise ValueError("slice_images: the ground-truth volume is on %s, the engine on %s" % (vd, self.device))
+            self._check_volume("slice_images", volume)
         cost = chomp_eps is not None
 
         def out(want, *shape, dtype=torch.float32):

@@ -72,9 +72,7 @@ class FrameData:
         if isinstance(data, np.ndarray):     # host twins / frame ids
             return np.concatenate((batch, data))
         n, k = batch.shape[0], data.shape[0]
-        back = getattr(self, "_back", None)
-        if back is None:
-            back = self._back = {}
+        back = self._back
         buf = back.get(name)
         if (buf is None or buf.data_ptr() != batch.data_ptr() or buf.shape[0] < n + k or buf.dtype != data.dtype
                 or buf.device != data.device or buf.shape[1:] != data.shape[1:]):
@@ -91,7 +89,7 @@ class FrameData:
         """Move frame_avg_losses into pinned host memory (one synchronising copy; later growth stays there).  No-op when they
         already are, when `host_losses` is off, or on a host without a HIP device."""
         fal = self.frame_avg_losses
-        if fal is None or not getattr(self, "host_losses", True) or fal.device.type != "cuda":
+        if fal is None or not self.host_losses or fal.device.type != "cuda":
             return False
         n = fal.shape[0]
         buf = torch.empty(max(2 * n, 8), dtype=fal.dtype, pin_memory=True)

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from .engine import _stream, to_host
 
 
 def grid_index_to_world(dim, scene_scale, bounds_transform):
@@ -61,7 +62,6 @@ class Mesher:
         return verts, faces, normals, nv, nf
 
     def __call__(self, volume, level=0.0, index_to_world=None, capacity=None):
-        from .engine import _stream
         if volume.dim() != 3:
             raise ValueError("marching_cubes takes a [D0, D1, D2] volume (got shape %s)" % (tuple(volume.shape),))
         vol = volume.detach().to(device=self.device, dtype=torch.float32).contiguous()
@@ -112,3 +112,58 @@ def marching_cubes(volume, level=0.0, index_to_world=None):
     if m is None:
         m = _MESHERS[key] = Mesher(torch.device("cuda", key))
     return m(volume, level, index_to_world)
+
+
+class MeshMethods:
+    """The trainer-level half (trainer.py:1426-1443,1500-1542): a base class of hot_path.HotPath; `self` is the grafted Trainer."""
+
+    def get_sdf_grid(self):
+        """The network on the cached `grid_pc` as a [grid_dim]^3 volume: ONE forward launch over all grid_dim^3 points (the
+        reference's fc_map.chunks makes one per 100 000; the kernel's result per point does not depend on the chunking)."""
+        d = self.grid_dim
+        with torch.no_grad():
+            return self.engine.sdf_eval(self.grid_pc).view(d, d, d)
+
+    def _vis_pointcloud(self):
+        """world-frame point cloud of the keyframes at visualisation resolution (update_vis_vars + backproject + draw_pc)"""
+        ref = self._hip.ref_module
+        self.update_vis_vars()
+        pcs_cam = ref.geometry.transform.backproject_pointclouds(self.gt_depth_vis, self.fx_vis, self.fy_vis, self.cx_vis,
+                                                                 self.cy_vis)
+        pc, _ = ref.draw3D.draw_pc(len(self.frames), pcs_cam, self.frames.T_WC_batch_np)
+        return pc
+
+    def mesh_rec(self, crop_mesh_with_pc=True):
+        """The reconstructed mesh as a trimesh.Trimesh in world coordinates, what the reference's mesh_rec returns.
+
+        Contract kept: a trainer without a GT scene that runs incrementally first re-derives its scene bounds from the keyframes'
+        point cloud (set_scene_properties); with crop_mesh_with_pc, faces none of whose vertices lie within crop_dist of that
+        point cloud are dropped (a KDTree query on the host) together with the vertices left unreferenced; a pending grid size
+        (new_grid_dim / new_grid_pc) is swapped in at the end.  The point cloud is only built when one of the two needs it.
+
+        The mesh itself: get_sdf_grid, then Engine.marching_cubes with draw_mesh's index -> world chain as the kernel's affine
+        (isdf_amd.mesh.grid_index_to_world), so vertices and normals come out in world coordinates; ONE device -> host copy;
+        flat grey face colours as draw_mesh(..., color_by="none") sets them."""
+        ref = self._ref("mesh_rec", "trimesh", "trimesh, KDTree, draw3D")
+        rescale = self.gt_scene is False and self.incremental
+        pc = self._vis_pointcloud() if (crop_mesh_with_pc or rescale) else None
+        if rescale:
+            self.set_scene_properties(ref.trimesh.PointCloud(pc))
+        sdf = self.get_sdf_grid()
+        A = grid_index_to_world(self.grid_dim, self.scene_scale_np, self.bounds_transform_np)
+        verts, faces, normals = self.engine.marching_cubes(sdf, 0.0, A)
+        nv = verts.shape[0]
+        verts_h, normals_h, faces_h = to_host(verts, normals, faces)
+        if crop_mesh_with_pc:
+            near = ref.KDTree(pc).query(verts_h, k=1)[0] < self.crop_dist
+            faces_h = faces_h[near[faces_h].any(axis=1)]
+            used = np.zeros(nv, bool)
+            used[faces_h.reshape(-1)] = True
+            remap = np.cumsum(used) - 1
+            verts_h, normals_h, faces_h = verts_h[used], normals_h[used], remap[faces_h].astype(np.int32)
+        mesh = ref.trimesh.Trimesh(vertices=verts_h, vertex_normals=normals_h, faces=faces_h)
+        mesh.visual.face_colors = [160, 160, 160, 255]
+        if self.new_grid_dim is not None:
+            self.grid_dim, self.grid_pc = self.new_grid_dim, self.new_grid_pc
+            self.new_grid_dim = self.new_grid_pc = None
+        return mesh

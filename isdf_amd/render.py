@@ -11,9 +11,11 @@ The range source is one of: `scalar_range=(min, max)` (coarse pass of latest_fra
 keyed by (seed, counter)."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _ffi
+from .engine import _stream, to_host
 
 
 class Renderer:
@@ -41,7 +43,6 @@ class Renderer:
 
     def __call__(self, T_WC, dirs_C, H, W, n_samples=0, scalar_range=None, depth_images=None, min_depth=0.0, upsample=None,
                  depth_offset=0.0, draws=None, seed=0, counter=0, depth=None, want_depth=True, want_normals=False):
-        from .engine import _stream
         eng, dev = self.engine, self.engine.device
         f32 = lambda t: None if t is None else t.detach().to(device=dev, dtype=torch.float32).contiguous()
         T = f32(T_WC).reshape(-1, 4, 4)
@@ -81,3 +82,89 @@ class Renderer:
                    "isdf_render_views")
         self.calls += 1
         return out_d, out_n
+
+
+class RenderMethods:
+    """The trainer-level half (trainer.py:1055-1147,1225-1280): a base class of hot_path.HotPath; `self` is the grafted Trainer."""
+
+    def _render_rng(self, B, R, S):
+        """uniforms of one render pass: rng "torch" draws torch.rand(R, S) per view on the trainer's device, in the reference's
+        order (sample.py:123) -> dict(draws=[B, R, S]); "philox" advances the render counter (visualisation only: not part of
+        hip_state_dict) and leaves the torch generator alone"""
+        hip = self._hip
+        if hip.rng == "torch":
+            return dict(draws=torch.stack([torch.rand(R, S, device=self.device) for _ in range(B)]))
+        hip.render_count += 1
+        return dict(seed=hip.seed, counter=hip.render_count)
+
+    def _vis_poses(self):
+        T_WC_batch = self.frames.T_WC_batch
+        if self.frames.T_WC_track:                 # trainer.py:1229-1231 (a truthy track: a list of [4, 4] poses or a one-pose tensor)
+            T_WC_batch = self.frames.T_WC_track
+        if isinstance(T_WC_batch, (list, tuple)):
+            T_WC_batch = torch.stack([torch.as_tensor(t).reshape(4, 4) for t in T_WC_batch])
+        return T_WC_batch
+
+    def render_depth_vis(self):
+        """[K, H_vis, W_vis] depth of every keyframe from the map, on the device: ONE isdf_render_views pass over the K poses, the
+        depth range [min_depth, cv2.resize(depth, INTER_LINEAR) + 0.8] read from the device depth_batch (no host resize, no
+        upload), n_strat_samples stratified samples, first crossing.  No host synchronisation."""
+        K, H, W, S = len(self.frames), self.H_vis, self.W_vis, self.n_strat_samples
+        T = self._vis_poses()[:K]
+        rng = self._render_rng(K, H * W, S)
+        with torch.no_grad():
+            depth, _ = self.engine.render_views(T, self.dirs_C_vis[0], H, W, S, depth_images=self.frames.depth_batch[:K],
+                                                min_depth=self.min_depth, depth_offset=0.8, **rng)
+        return depth.view(K, H, W)
+
+    def render_normals_vis(self, view_depths):
+        """[K, H_vis, W_vis, 3] camera-frame normals at the given depths (render.render_normals per keyframe, render.py:38-57):
+        one pass of points, forward with input gradient and rotation by the inverse of each pose's 3x3 block."""
+        K, H, W = len(self.frames), self.H_vis, self.W_vis
+        T = self._vis_poses()[:K]
+        with torch.no_grad():
+            _, normals = self.engine.render_views(T, self.dirs_C_vis[0], H, W, depth=view_depths.reshape(K, H * W))
+        return normals.view(K, H, W, 3)
+
+    def latest_frame_vis(self, do_render=True):
+        """The reference's (rgbd_vis, render_vis, T_WC_np) and timing line.  The renders run on the device: a coarse pass of 20
+        samples over [min_depth, max_depth] on dirs_C_vis, the align-corners upsample and a fine pass of 12 samples over
+        d +- 0.1 on dirs_C_vis_up (in-kernel), normals at the fine depth; depth and normal image come back in one copy.
+        The host image work (cv2.resize, imgviz.depth2rgb, hstack) is the reference module's own.  do_render=False is the
+        reference's path."""
+        if not do_render:
+            return super().latest_frame_vis(do_render=False)
+        ref = self._hip.ref_module
+        start, end = ref.start_timing()
+        if self.live:
+            data = self.scene_dataset[0]
+            image, depth, T_WC_np = data['image'], data['depth'], data['T']
+        else:
+            image = self.frames.im_batch_np[-1]
+            depth = self.frames.depth_batch_np[-1]
+            T_WC_np = self.frames.T_WC_batch_np[-1]
+        w, h = self.W_vis_up * 2, self.H_vis_up * 2
+        image = ref.cv2.resize(image, (w, h))
+        depth = ref.cv2.resize(depth, (w, h))
+        depth_viz = ref.imgviz.depth2rgb(depth, min_value=self.min_depth, max_value=self.max_depth)
+        rgbd_vis = np.hstack((image, depth_viz))
+
+        T_WC = torch.FloatTensor(T_WC_np).to(self.device)[None, ...]
+        Hc, Wc, Hu, Wu = self.H_vis, self.W_vis, self.H_vis_up, self.W_vis_up
+        rng_c = self._render_rng(1, Hc * Wc, 20)
+        rng_f = self._render_rng(1, Hu * Wu, 12)
+        eng = self.engine
+        with torch.no_grad():
+            coarse, _ = eng.render_views(T_WC, self.dirs_C_vis, Hc, Wc, 20, scalar_range=(self.min_depth, self.max_depth),
+                                         **rng_c)
+            fine, normals = eng.render_views(T_WC, self.dirs_C_vis_up, Hu, Wu, 12, upsample=coarse.view(1, Hc, Wc),
+                                             depth_offset=0.1, want_normals=True, **rng_f)
+            normals = torch.clip((-normals + 1.0) / 2.0, 0., 1.)
+            render_depth, normals = to_host(fine.reshape(Hu, Wu), normals.reshape(Hu, Wu, 3))
+        render_depth_viz = ref.imgviz.depth2rgb(render_depth, min_value=self.min_depth, max_value=self.max_depth)
+        normals_viz = (normals * 255).astype(np.uint8)
+        render_vis = np.hstack((normals_viz, render_depth_viz))
+        render_vis = ref.cv2.resize(render_vis, (int(render_vis.shape[1] * 2), int(render_vis.shape[0] * 2)))
+        elapsed = ref.end_timing(start, end)
+        print("Time for depth and normal render", elapsed)
+        return rgbd_vis, render_vis, T_WC_np

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from .engine import to_host
 
 
 def _rgb_bytes(c):
@@ -95,3 +96,138 @@ def plane(engine, origin, du, dv, H, W, cmap, gt_volume=None, chomp_eps=None, oo
     out = slice_images(engine, pts, cmap, gt_volume, chomp_eps, oob_fill)
     out.pts = pts
     return out
+
+
+class SliceMethods:
+    """The trainer-level half (trainer.py:1446-1481,1558-1815): a base class of hot_path.HotPath; `self` is the grafted Trainer."""
+
+    def _slice_colormap(self, mappable):
+        """the reference's ScalarMappable as an isdf_amd.slices.Colormap, made (and uploaded) once per distinct table"""
+        cm = Colormap.from_scalar_mappable(mappable)
+        return self._hip.slice_cmaps.setdefault(cm.key(), cm)
+
+    def compute_slices(self, z_ixs=None, n_slices=6, include_gt=False, include_diff=False, include_chomp=False,
+                       draw_cams=False, sdf_range=[-2, 2]):
+        """The reference's dict of lists of uint8 images (pred_sdf, and gt_sdf / pred_cost / gt_cost / diff where asked for;
+        trainer.py:1558-1707).  The slices are selected from grid_pc on the device as the reference selects them; ONE forward
+        launch over all of them and ONE isdf_slice_images pass give the colours of the prediction and of the ground truth (the
+        device copy of gt_sdf_interp's grid, fill 0 outside it) and both CHOMP cost fields; one copy to the host.  The colour map
+        is the reference module's own sdf_util.get_colormap (which edits `sdf_range` in place, as there); cv2.resize,
+        imgviz.depth2rgb and the camera markers are the reference module's own calls on the host.  `diff` is the all-white image
+        the reference returns (it discards the difference it computes, trainer.py:1647-1671): nothing is computed for it."""
+        ref = self._ref("compute_slices", "sdf_util", "sdf_util.get_colormap, cv2, imgviz")
+        if z_ixs is None:
+            z_ixs = torch.linspace(30, self.grid_dim - 30, n_slices)
+            z_ixs = torch.round(z_ixs).long()
+        z_ixs = z_ixs.to(self.device)
+        pc = self.grid_pc.reshape(self.grid_dim, self.grid_dim, self.grid_dim, 3)
+        pc = torch.index_select(pc, self.up_ix, z_ixs)
+        if not self.up_aligned:
+            indices = np.arange(len(z_ixs))[::-1]
+            indices = torch.from_numpy(indices.copy()).to(self.device)
+            pc = torch.index_select(pc, self.up_ix, indices)
+        cmap = self._slice_colormap(ref.sdf_util.get_colormap(sdf_range=sdf_range))
+        grid_shape = tuple(pc.shape[:-1])
+        n_slices = grid_shape[self.up_ix]
+        scales = torch.cat([self.scene_scale[:self.up_ix], self.scene_scale[self.up_ix + 1:]])
+        im_size = 256 * scales / scales.min()
+        im_size = im_size.int().cpu().numpy()
+
+        res = slice_images(self.engine, pc, cmap, gt_volume=self._gt_volume() if include_gt else None,
+                              chomp_eps=2. if include_chomp else None, oob_fill=0.)
+        pred_rgb, gt_rgb, pred_cost, gt_cost = to_host(res.pred_rgb, res.gt_rgb, res.pred_cost, res.gt_cost)
+
+        def resized(viz):
+            return [ref.cv2.resize(np.take(viz, i, self.up_ix), im_size[::-1]) for i in range(n_slices)]
+
+        def cost_images(cost):
+            viz = ref.imgviz.depth2rgb(cost.reshape(self.grid_dim, -1), min_value=0., max_value=1.5)
+            return resized(viz.reshape(*grid_shape, 3))
+        slices = {"pred_sdf": resized(pred_rgb)}
+        if include_chomp:
+            slices["pred_cost"] = cost_images(pred_cost)
+        if include_gt:
+            slices["gt_sdf"] = resized(gt_rgb)
+            if include_chomp:
+                slices["gt_cost"] = cost_images(gt_cost.astype(np.float64))      # the reference's ground truth is float64
+        if include_diff:
+            if not include_gt:       # the reference reads its gt_sdf here, which only include_gt assigns (trainer.py:1643)
+                raise UnboundLocalError("local variable 'gt_sdf' referenced before assignment")
+            slices["diff"] = resized(np.full(grid_shape + (3,), 255, dtype=np.uint8))
+
+        if draw_cams:       # the reference's markers (trainer.py:1673-1705), its own draw / cv2 calls
+            cam_xyz = self.frames.T_WC_batch[:, :3, 3].cpu()
+            cam_td = self.to_topdown(cam_xyz, im_size)
+            cam_rots = self.frames.T_WC_batch[:, :3, :3].cpu().numpy()
+            angs = [np.arctan2(rot[0, 2], rot[0, 0]) for rot in cam_rots]
+            for i, im in enumerate(slices["pred_sdf"]):
+                if self.incremental:
+                    trajectory_gt = self.frames.T_WC_batch_np[:, :3, 3]
+                    if self.frames.T_WC_gt is not None:
+                        trajectory_gt = self.frames.T_WC_gt[:, :3, 3]
+                    traj_td = self.to_topdown(trajectory_gt, im_size)
+                    for j in range(len(traj_td) - 1):
+                        if not (traj_td[j] == traj_td[j + 1]).all():
+                            im = im.astype(np.uint8) / 255
+                            im = ref.cv2.line(im, traj_td[j][::-1], traj_td[j + 1][::-1], [1., 0., 0.], 2)
+                            im = (im * 255).astype(np.uint8)
+                for (p, ang) in zip(cam_td, angs):
+                    ref.draw.draw_agent(im, p, agent_rotation=ang, agent_radius_px=12)
+                slices["pred_sdf"][i] = im
+        return slices
+
+    def obj_slices_vis(self, n_slices=6):
+        """The reference's stacked image (per object the predicted slices over the ground-truth ones), or None without an
+        obj_bounds_file (trainer.py:1775-1815): per object the reference's own 256 x n_slices x 256 points, one forward launch
+        and one isdf_slice_images pass (colours of both, map [-0.5, 0.5]); the two images come back in one copy."""
+        if self.obj_bounds_file is None:
+            return None
+        ref = self._ref("obj_slices_vis", "sdf_util", "sdf_util.get_colormap, metrics")
+        up_ix = 1
+        obj_bounds = ref.metrics.get_obj_eval_bounds(self.obj_bounds_file, up_ix)
+        cmap = self._slice_colormap(ref.sdf_util.get_colormap(sdf_range=[-0.5, 0.5]))
+        vol = self._gt_volume()
+        all_slices = []
+        for bounds in obj_bounds:
+            dims = [256, 256, 256]
+            dims[up_ix] = n_slices
+            x = torch.linspace(bounds[0, 0], bounds[1, 0], dims[0])
+            y = torch.linspace(bounds[0, 1], bounds[1, 1], dims[1])
+            z = torch.linspace(bounds[0, 2], bounds[1, 2], dims[2])
+            xx, yy, zz = torch.meshgrid(x, y, z, indexing="ij")
+            pc = torch.cat((xx[..., None], yy[..., None], zz[..., None]), dim=3).to(self.device)
+            res = slice_images(self.engine, pc, cmap, gt_volume=vol, oob_fill=0.)
+            col, gt_col = to_host(res.pred_rgb, res.gt_rgb)
+            col = np.hstack([col[:, i] for i in range(n_slices)])
+            gt_col = np.hstack([gt_col[:, i] for i in range(n_slices)])
+            all_slices.append(np.vstack((col, gt_col)))
+        return np.vstack((all_slices))
+
+    def get_sdf_grid_pc(self, include_gt=False, mask_near_pc=False):
+        """(sdf_grid_pc, keep_mask) of the reference (trainer.py:1446-1481): grid_pc with the network's value as a float32
+        [d, d, d, 4] array -- with include_gt (and a ground-truth grid) float64 [d, d, d, 5], the last column the ground truth with
+        0 outside its volume, from the device lookup --, and with mask_near_pc the boolean [.., .., ..] mask of the grid points
+        whose every-tenth representative lies within crop_dist of the keyframes' point cloud (Engine.nn_distance instead of a
+        host KD-tree), repeated as the reference repeats it; else None.  One forward launch, one copy to the host."""
+        d = self.grid_dim
+        sdf_grid = self.get_sdf_grid()
+        grid_pc = self.grid_pc.reshape(d, d, d, 3)
+        sdf_grid_pc = torch.cat((grid_pc, sdf_grid[..., None]), dim=-1)
+        with_gt = include_gt and self.gt_sdf_interp is not None
+        if with_gt:
+            gt = self.engine.slice_images(self.grid_pc, None, None, self._gt_volume(), None, oob_fill=0.)[1]
+            sdf_grid_pc = torch.cat((sdf_grid_pc, gt.view(d, d, d, 1)), dim=-1)
+            self.gt_sdf_interp.fill_value = 0.0           # the state the reference leaves its interpolator in (trainer.py:1454-1461)
+            self.gt_sdf_interp.bounds_error = True
+        near = None
+        if mask_near_pc:
+            pc = np.ascontiguousarray(self._vis_pointcloud(), dtype=np.float32)
+            sparse = sdf_grid_pc[::10, ::10, ::10, :3]
+            dist, _, _ = self.engine.nn_distance(sparse.reshape(-1, 3), torch.from_numpy(pc).reshape(-1, 3).to(self.device))
+            near = (dist.double() < self.crop_dist).view(sparse.shape[:-1])
+        sdf_grid_pc, keep_mask = to_host(sdf_grid_pc.detach(), near)
+        if with_gt:
+            sdf_grid_pc = sdf_grid_pc.astype(np.float64)
+        if keep_mask is not None:
+            keep_mask = keep_mask.repeat(10, axis=0).repeat(10, axis=1).repeat(10, axis=2)
+        return sdf_grid_pc, keep_mask
