@@ -111,7 +111,7 @@ int isdf_sdf_eval(const isdf_net_cfg* net, const float* params, const void* shad
   if (n_points == 0) return ISDF_OK;
   ChainParams p = {};
   p.lay = l; p.params = params; p.shadow = (const uint16_t*)shadow; p.pts = pts; p.noise = noise;
-  p.n_points_host = n_points; p.S = 1; p.sdf = sdf; p.sdf_grad = sdf_grad;
+  p.n_points_host = n_points; p.pts_capacity = n_points; p.S = 1; p.sdf = sdf; p.sdf_grad = sdf_grad;
   const int mode = sdf_grad ? 1 : 0;
   WorkspaceLayout w; make_workspace(l, n_points, 0, false, &w);
   if (mode == 1) {
@@ -180,7 +180,7 @@ static int train_step_impl(const isdf_net_cfg* net, const isdf_loss_cfg* loss, c
 
   ChainParams p = {};
   p.lay = l; p.loss = *loss; p.params = params; p.shadow = (const uint16_t*)shadow;
-  p.pts = a->pc; p.noise = a->noise; p.n_valid = a->n_valid; p.S = a->S;
+  p.pts = a->pc; p.pts_capacity = maxPts; p.noise = a->noise; p.n_valid = a->n_valid; p.S = a->S;
   p.noise_std = a->noise_std; p.noise_seed = a->noise_seed; p.noise_off = a->noise_offset;
   p.z_vals = a->z_vals; p.depth = a->depth_sample; p.dirsC = a->dirs_C_sample; p.dirsW = a->dirs_W_sample;
   p.normals = a->norm_sample; p.pc_bounds = a->pc_bounds; p.pc_grad_vec = a->pc_grad_vec;
@@ -196,7 +196,8 @@ static int train_step_impl(const isdf_net_cfg* net, const isdf_loss_cfg* loss, c
   if (ev && hipEventRecord(ev[1], st) != hipSuccess) return ISDF_EHIP;
 
   DwParams d = {};
-  d.lay = l; d.sp = w.sp; d.spill = p.spill; d.pe_aux = p.pe_aux; d.n_valid = a->n_valid; d.S = a->S; d.dwPart = dwPart;
+  d.lay = l; d.sp = w.sp; d.spill = p.spill; d.pe_aux = p.pe_aux; d.n_valid = a->n_valid; d.S = a->S; d.cap_tiles = (int32_t)w.nTiles;
+  d.dwPart = dwPart;
   rc = launch_dw(d, st);
   if (rc) return rc;
   if (ev && hipEventRecord(ev[2], st) != hipSuccess) return ISDF_EHIP;

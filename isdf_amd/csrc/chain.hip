@@ -71,6 +71,9 @@ struct Tile {
 // of a weight load would put its HBM round trip into the MFMA stream, and requesting earlier costs
 // registers the 128-VGPR budget does not have (measured variants: profiles/r02_ab_chain_variants.txt; issuing the
 // requests behind the LAST weight request in the middle of the GEMM measured +2 .. +9 %: profiles/r03_whatif_spill_traffic.txt).
+// The forward layers hang their epilogue's parameter vectors (bias; w_out and b_out at the top) on the same hook, so no epilogue
+// opens with a round trip of its own.  PRE: chunk 0 is already on its way into `wq` -- the kernel's prologue requests layer 0's
+// next to the points, in front of the PE stage -- and the GEMM starts at its first MFMA.
 template <int FBN, int CKF> struct WChunk { uint4 v[CKF / FBN][FBN]; };   // one chunk of packed weight fragments (32 VGPRs)
 struct WRef { int soff; int rb; };   // byte offset of a wave's slice of a packed matrix in the shadow buffer + row-block stride (bytes)
 
@@ -88,7 +91,7 @@ __device__ __forceinline__ void load_w(WChunk<FBN, CKF>& wq, rsrc_t rw, WRef r, 
 // 16 * FBN * PBN v_mov_b32 zeroing the registers beforehand (8 % of the kernel's VALU instructions).
 // TWO: every weight fragment also multiplies a SECOND activation operand at column colByteBase2 (W a_hi + W a_lo of a compensated
 // layer in one pass over W: the vector-memory path is the kernel's busiest unit, a second pass would fetch the matrix again).
-template <bool F16, int KSTEPS, int FBN, int PBN, int ROWB, int CKF, bool ZERO = false, bool TWO = false, typename Hook>
+template <bool F16, int KSTEPS, int FBN, int PBN, int ROWB, int CKF, bool ZERO = false, bool TWO = false, bool PRE = false, typename Hook>
 __device__ __forceinline__ void gemm(f32x16 (&acc)[FBN][PBN], WChunk<FBN, CKF>& wq, rsrc_t rw, WRef wr, const char* xl,
                                      int colByteBase, int lane, Hook&& postHook, int colByteBase2 = 0) {
   constexpr int CK = CKF / FBN;                  // k-steps per chunk: CK*FBN uint4 = 32 VGPRs
@@ -102,7 +105,7 @@ __device__ __forceinline__ void gemm(f32x16 (&acc)[FBN][PBN], WChunk<FBN, CKF>& 
   // (point block, region, ks>>3) being immediate offsets.
   const int xlane = j * ROWB + ((hi * 16) ^ ((j & 15) << 4));   // byte offset from the tile base (kept an offset so the LDS address space survives)
   const int lane16 = lane * 16;
-  load_w(wq, rw, wr, lane16, 0);
+  if constexpr (!PRE) load_w(wq, rw, wr, lane16, 0);
   // One chunk: the activation operand is read one k-step ahead of the MFMAs that consume it; the weight registers are
   // re-requested for the next chunk after the chunk's last MFMA.
   auto chunk = [&](int ch, auto refill, auto zero) {
@@ -204,9 +207,61 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
     xw = j * ROWB + 8 * hi + (((j & 15) << 4) ^ (((w * FB) & 3) * 64)) + ((w * FB) >> 2) * 256;
   };
   refresh();
-  const int64_t P = p.n_valid ? (int64_t)(*p.n_valid) * p.S : p.n_points_host;
   const int64_t n0 = (int64_t)blockIdx.x * BM;
+  const rsrc_t rsW = make_rsrc(p.shadow, 0x7fffffffu);
+  // feature index of (fb, qp) blocks: f0 = ubase(fb, qp) + 4*hi
+  auto ubase = [&](int fb, int qp) { return w * (FB * 32) + fb * 32 + 16 * qp; };
+  // 8 fp32 parameters of a per-unit vector (a bias, w_out) at flat offset vecBase: units ub + 4*hq + {0..3, 8..11} (hq = the lane's
+  // half, lane >> 5).  Units >= L.H are padding (a hidden width below the tile width, NetLayout::H): they read as 0 and nothing past
+  // the real vector is touched.
+  auto ld_params8 = [&](int vecBase, int ub, int hq, float (&o)[8]) {
+    // a buffer descriptor over exactly this vector: every dword at or beyond unit L.H is out of range and reads as 0 (the range check of
+    // a raw buffer load is per dword), so a narrower net needs no mask and no branch here
+    const rsrc_t rv = make_rsrc(p.params + vecBase, (uint32_t)L.H * 4u);
+    const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rv, 16 * hq, ub * 4, 0);
+    const u32x4 b = __builtin_amdgcn_raw_buffer_load_b128(rv, 16 * hq + 32, ub * 4, 0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o[e] = __uint_as_float(a[e]); o[4 + e] = __uint_as_float(b[e]); }
+  };
+  const int rbW = w * FB;  // first 32-row block of this wave
+  auto wptr = [&](int64_t set, int64_t matOff, int kp) {
+    return WRef{(int)((set + matOff) * 2) + rbW * (kp / 16) * 1024, (kp / 16) * 1024};
+  };
+  auto fwdW = [&](int64_t set, int li) {   // forward-orientation matrix of layer li (K = EP | HD+EP | HD)
+    return wptr(set, L.fwdMat[li], li == 0 ? EP : (li == L.cat ? HD + EP : HD));
+  };
+  WChunk<FB, T::CKF> wq;   // the weight-fragment registers of the running gemm
+  WChunk<FB, T::CKF / 2> wq2;   // ... of a two-operand gemm: half the k-steps per chunk, twice the activation registers
+  // ------------------------------------------------------------------ prologue: ONE memory round trip
+  // Everything the tile needs in front of its first MFMA is requested at once: n_valid, the tile's points, chunk 0 of layer 0's weights
+  // (into the weight registers, idle until that GEMM: gemm<PRE>) and layer 0's bias and b_out.  (Until round 7 these were three
+  // DEPENDENT round trips -- n_valid, then the points, then, behind the PE stage, the weights: 14.7 k cycles in front of the first
+  // GEMM, profiles/r05_ab_chain_pe_stages.txt; the numbers since: profiles/r07_prologue_round_trips.txt.)  A workgroup does not know yet
+  // whether it has any point, so nothing here is a flat load: the points come through a descriptor over THIS TILE's rows clipped to the
+  // buffer's capacity (rows at or beyond it read as 0 and touch nothing; an empty descriptor for a tile beyond it), the weights and
+  // the parameter vectors through theirs, at offsets that do not depend on the tile.  Rows at or beyond n_valid * S are masked once
+  // both answers are in; a workgroup with none leaves then.
+  // (n_valid through a descriptor as well, FIRST: the memory counter retires in order, so the wait for it leaves the rest in flight;
+  // a null n_valid -- the forward-only call -- is an empty descriptor and no access)
+  int nvRaw = (int)__builtin_amdgcn_raw_buffer_load_b32(make_rsrc(p.n_valid, p.n_valid ? 4u : 0u), 0, 0, 0);
+  const int prow = (!WIDE_E && BM == 64) ? (tid & 63) : (tid % (BM / T::NW)) + (BM / T::NW) * (tid / 64);   // the row this thread embeds (PE stage)
+  const int64_t capLeft = p.pts_capacity - n0;
+  const rsrc_t rsP = make_rsrc(p.pts + n0 * 3, (uint32_t)(capLeft < 0 ? 0 : (capLeft < BM ? capLeft : BM)) * 12u);
+  float px0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsP, prow * 12, 0, 0));
+  float px1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsP, prow * 12 + 4, 0, 0));
+  float px2 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsP, prow * 12 + 8, 0, 0));
+  if constexpr (X2ALL) load_w(wq2, rsW, fwdW(L.setFwdA, 0), lane16, 0);
+  else load_w(wq, rsW, fwdW(L.setFwdA, 0), lane16, 0);
+  float bvq[FB][2][8];      // the running forward layer's bias, per (fb, qp) block
+#pragma unroll
+  for (int fb = 0; fb < FB; ++fb)
+#pragma unroll
+    for (int qp = 0; qp < 2; ++qp) ld_params8(L.offB[0], ubase(fb, qp), hi, bvq[fb][qp]);
+  const float b_out = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(make_rsrc(p.params + L.offBout, 4u), 0, 0, 0));
+  asm volatile("" : "+v"(nvRaw) : : "memory");   // n_valid is consumed from here on: every request above stays in front of the wait for it
+  const int64_t P = p.n_valid ? (int64_t)__builtin_amdgcn_readfirstlane(nvRaw) * p.S : p.n_points_host;
   if (n0 >= P) return;
+  if (n0 + prow >= P) { px0 = 0.f; px1 = 0.f; px2 = 0.f; }
   const int nf = L.n_freqs;
   const float so = L.scale_output;
   ChainStamps TS(p.dbg, p.n_cu);   // phase time stamps of the -DISDF_DEBUG_HOOKS=1 build; empty inlines in the shipped kernel
@@ -232,7 +287,6 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
   const int64_t setFwdA = L.setFwdA, setFwdB = L.setFwdB, setBwdA = L.setBwdA, setBwdB = L.setBwdB, setFwdLo = L.setFwdLo;
   // this tile's block of the spill buffer ([tile][tensor][BM*HD] bf16)
   uint16_t* spillTile = p.spill + TS.spill_tile() * p.sp.tileStride;
-  const rsrc_t rsW = make_rsrc(p.shadow, 0x7fffffffu);
   const rsrc_t rsS = make_rsrc(spillTile, (uint32_t)(p.sp.tileStride * 2));   // loads (compiler-tracked)
   const i32x4 srdS = make_srd(spillTile, (uint32_t)(p.sp.tileStride * 2));     // stores (bstore16_nt)
   // byte offset of this wave's first piece of a spilled tensor (frag16 order, see frag16_off)
@@ -241,19 +295,6 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
   float* vecTile = MODE == 2 ? p.vec_part + (int64_t)blockIdx.x * p.vecStride : nullptr;
   const rsrc_t rsV = make_rsrc(vecTile, MODE == 2 ? (uint32_t)p.vecStride * 4u : 0u);
   (void)setFwdB; (void)setBwdB; (void)setFwdLo; (void)rsS; (void)rsV; (void)srdS;
-  // feature index of (fb, qp) blocks: f0 = ubase(fb, qp) + 4*hi
-  auto ubase = [&](int fb, int qp) { return w * (FB * 32) + fb * 32 + 16 * qp; };
-  // 8 fp32 parameters of a per-unit vector (a bias, w_out) at flat offset vecBase: units ub + 4*hi + {0..3, 8..11}.  Units >= L.H are
-  // padding (a hidden width below the tile width, NetLayout::H): they read as 0 and nothing past the real vector is touched.
-  auto ld_params8 = [&](int vecBase, int ub, float (&o)[8]) {
-    // a buffer descriptor over exactly this vector: every dword at or beyond unit L.H is out of range and reads as 0 (the range check of
-    // a raw buffer load is per dword), so a narrower net needs no mask and no branch here
-    const rsrc_t rv = make_rsrc(p.params + vecBase, (uint32_t)L.H * 4u);
-    const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rv, 16 * hi, ub * 4, 0);
-    const u32x4 b = __builtin_amdgcn_raw_buffer_load_b128(rv, 16 * hi + 32, ub * 4, 0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = __uint_as_float(a[e]); o[4 + e] = __uint_as_float(b[e]); }
-  };
   // per-workgroup partial of a bias / out-layer gradient entry: sum over the half-wave's 32 points
   // The 8 values of an accumulator block (features elemUniform + 4*hi + {0..3, 8..11}) go out in ONE store: after the butterflies
   // every lane holds all eight sums, lane j < 8 of each half keeps sum j and writes it to its feature.  (One store per VALUE made
@@ -277,12 +318,11 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
     // a scalar and its LDS address one v_xad of the lane's row base and swizzle, instead of a handful of per-lane integer operations
     // per 2-byte store.  Same arithmetic per value, so the same bits (sdf, d sdf / d x and the losses of a step came out bit-identical to
     // the previous library's, tools/train_ab_check.py).  Measured effect on this kernel: none (chain 184.9 -> 184.1 us same-box,
-    // profiles/r05_ab_chain_pe_stages.txt) -- the 14 k cycles in front of the first GEMM are the two DEPENDENT memory round trips of
-    // the prologue (n_valid, then the points), not this stage's instructions; kept because it is the simpler addressing.
+    // profiles/r05_ab_chain_pe_stages.txt) -- the 14 k cycles in front of the first GEMM were the DEPENDENT memory round trips of
+    // the prologue, not this stage's instructions (the prologue above asks for everything at once since round 7); kept because it is
+    // the simpler addressing.
     const int ln = tid & 63;
-    const int64_t n = n0 + ln;
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-    if (n < P) { x0 = p.pts[n * 3]; x1 = p.pts[n * 3 + 1]; x2 = p.pts[n * 3 + 2]; }
+    const float x0 = px0, x1 = px1, x2 = px2;   // (requested by the prologue; rows past the last point are 0)
     // transform_3D_grid (transform.py:287-304) then * scale (embedding.py:12-22)
     const float y0 = (L.T[0] * x0 + L.T[1] * x1 + L.T[2] * x2 + L.T[3]) * L.scale_input;
     const float y1 = (L.T[4] * x0 + L.T[5] * x1 + L.T[6] * x2 + L.T[7]) * L.scale_input;
@@ -314,9 +354,7 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
     // a wave = (BM / NW points) x (direction slices): rows are 1 KB apart, i.e. 8 banks -- 64 points per wave was 8-way conflicted
     const int pt = (tid % (BM / T::NW)) + (BM / T::NW) * (tid / 64), prt = (tid % 64) / (BM / T::NW);
     constexpr int NPART = (T::NW * 64) / BM;
-    const int64_t n = n0 + pt;
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-    if (n < P) { x0 = p.pts[n * 3]; x1 = p.pts[n * 3 + 1]; x2 = p.pts[n * 3 + 2]; }
+    const float x0 = px0, x1 = px1, x2 = px2;   // (pt == prow: requested by the prologue; rows past the last point are 0)
     // transform_3D_grid (transform.py:287-304) then * scale (embedding.py:12-22)
     float y0 = (L.T[0] * x0 + L.T[1] * x1 + L.T[2] * x2 + L.T[3]) * L.scale_input;
     float y1 = (L.T[4] * x0 + L.T[5] * x1 + L.T[6] * x2 + L.T[7]) * L.scale_input;
@@ -348,15 +386,6 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
 
   // ------------------------------------------------------------------ forward
   f32x16 acc[FB][PB];
-  const int rbW = w * FB;  // first 32-row block of this wave
-  auto wptr = [&](int64_t set, int64_t matOff, int kp) {
-    return WRef{(int)((set + matOff) * 2) + rbW * (kp / 16) * 1024, (kp / 16) * 1024};
-  };
-  auto fwdW = [&](int64_t set, int li) {   // forward-orientation matrix of layer li (K = EP | HD+EP | HD)
-    return wptr(set, L.fwdMat[li], li == 0 ? EP : (li == L.cat ? HD + EP : HD));
-  };
-  WChunk<FB, T::CKF> wq;   // the weight-fragment registers of the running gemm
-  WChunk<FB, T::CKF / 2> wq2;   // ... of a two-operand gemm: half the k-steps per chunk, twice the activation registers
   // iterate the wave's accumulator as (fb, pb, qp) blocks of 8 values:
   // values v[0..3] -> features f0..f0+3, v[4..7] -> f0+8..f0+11, point row = pb*32+j
   auto for_blocks2 = [&](auto&& fn, auto&& tail) {
@@ -499,38 +528,59 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
     *(uint2*)(X + (lb ^ 16)) = __builtin_bit_cast(uint2, hb);
     put_x(true, fb, pb, qp, r, LO);
   };
-  for (int li = 0; li < L.L; ++li) {
+  // One forward layer.  Layer 0 is PEELED (FIRST): its weight chunk and bias come from the prologue, and inside the layer loop those
+  // registers would be carried around the back edge -- live through every epilogue (measured at compile time: +40 VGPRs).
+  auto fwd_layer = [&](int li, auto firstTag) {
+    constexpr bool FIRST = decltype(firstTag)::value;
     refresh();
     // compensated layers (OPER 2): the cat layer adds W_lo[:, HD:] emb (the residual of its embedding columns; the one of
     // its hidden columns moves sdf by 3e-5 and is skipped), the layers past it W_lo a and W a_lo (a_lo sits in region 2,
     // which the forward pass no longer needs once the cat layer has consumed the embedding).  Numpy model of these
     // numerics vs the reference at BASELINE size: tests/precision_model.py, tools/studies/split_precision_study.py.
     const bool comp = X2 && (X2ALL || li >= L.cat);
-    if (li == 0) {
+    // The epilogue's parameter vectors ride on the postHook of the layer's LAST gemm (its weight registers are dead there), like the
+    // spill-tile requests of the other sweeps: the bias of a layer above 0 (layer 0's came with the prologue) and, at the top, w_out.
+    float wvq[FB][2][8];
+    auto top_params = [&] {
+      if (li != L.L - 1) return;
+#pragma unroll
+      for (int fb = 0; fb < FB; ++fb)
+#pragma unroll
+        for (int qp = 0; qp < 2; ++qp) ld_params8(L.offWout, ubase(fb, qp), lane >> 5, wvq[fb][qp]);
+    };
+    auto fwd_params = [&] {
+#pragma unroll
+      for (int fb = 0; fb < FB; ++fb)
+#pragma unroll
+        for (int qp = 0; qp < 2; ++qp) ld_params8(L.offB[li], ubase(fb, qp), lane >> 5, bvq[fb][qp]);
+      top_params();
+    };
+    if constexpr (FIRST) {   // layer 0 (chunk 0 of its first gemm was requested by the prologue: PRE)
       if (X2ALL) {   // W (emb + emb_lo) in one pass over W, then W_lo emb
-        gemm<F16, EP / 16, FB, PB, ROWB, T::CKF / 2, true, true>(acc, wq2, rsW, fwdW(setFwdA, li), X, HD * 2, lane, [] {}, (LO + HD) * 2);
-        gemm<F16, EP / 16, FB, PB, ROWB, T::CKF>(acc, wq, rsW, fwdW(setFwdLo, li), X, HD * 2, lane, [] {});
+        gemm<F16, EP / 16, FB, PB, ROWB, T::CKF / 2, true, true, true>(acc, wq2, rsW, fwdW(setFwdA, li), X, HD * 2, lane, [] {}, (LO + HD) * 2);
+        gemm<F16, EP / 16, FB, PB, ROWB, T::CKF>(acc, wq, rsW, fwdW(setFwdLo, li), X, HD * 2, lane, top_params);
       } else {
-        gemm<F16, EP / 16, FB, PB, ROWB, T::CKF, true>(acc, wq, rsW, fwdW(setFwdA, li), X, HD * 2, lane, [] {});
+        gemm<F16, EP / 16, FB, PB, ROWB, T::CKF, true, false, true>(acc, wq, rsW, fwdW(setFwdA, li), X, HD * 2, lane, top_params);
       }
     } else if (li == L.cat) {
+      constexpr bool LO3 = X2 && !X2ALL;   // comp here: a third gemm over the residual of the embedding columns closes the layer
       if (X2ALL) {   // W ([a | emb] + [a_lo | emb_lo]) in one pass over W, then W_lo [a | emb]
         gemm<F16, (HD + EP) / 16, FB, PB, ROWB, T::CKF / 2, true, true>(acc, wq2, rsW, fwdW(setFwdA, li), X, 0, lane, [] {}, LO * 2);
-        gemm<F16, (HD + EP) / 16, FB, PB, ROWB, T::CKF>(acc, wq, rsW, fwdW(setFwdLo, li), X, 0, lane, [] {});
+        gemm<F16, (HD + EP) / 16, FB, PB, ROWB, T::CKF>(acc, wq, rsW, fwdW(setFwdLo, li), X, 0, lane, fwd_params);
       } else {
-        gemm<F16, (HD + EP) / 16, FB, PB, ROWB, T::CKF, true>(acc, wq, rsW, fwdW(setFwdA, li), X, 0, lane, [] {});
+        gemm<F16, (HD + EP) / 16, FB, PB, ROWB, T::CKF, true>(acc, wq, rsW, fwdW(setFwdA, li), X, 0, lane, [&] { if constexpr (!LO3) fwd_params(); });
       }
-      if (!X2ALL && comp) {
+      if constexpr (LO3) {
         WRef wl = fwdW(setFwdLo, li);
         wl.soff += (HD / 16) * 1024;   // k-steps HD/16 .. of every row block: the embedding columns
-        gemm<F16, EP / 16, FB, PB, ROWB, T::CKF>(acc, wq, rsW, wl, X, HD * 2, lane, [] {});
+        gemm<F16, EP / 16, FB, PB, ROWB, T::CKF>(acc, wq, rsW, wl, X, HD * 2, lane, fwd_params);
       }
     } else {
       if (comp) {   // W (a + a_lo) in one pass over W, then W_lo a
         gemm<F16, HD / 16, FB, PB, ROWB, T::CKF / 2, true, true>(acc, wq2, rsW, fwdW(setFwdA, li), X, 0, lane, [] {}, LO * 2);
-        gemm<F16, HD / 16, FB, PB, ROWB, T::CKF>(acc, wq, rsW, fwdW(setFwdLo, li), X, 0, lane, [] {});
+        gemm<F16, HD / 16, FB, PB, ROWB, T::CKF>(acc, wq, rsW, fwdW(setFwdLo, li), X, 0, lane, fwd_params);
       } else {
-        gemm<F16, HD / 16, FB, PB, ROWB, T::CKF, true>(acc, wq, rsW, fwdW(setFwdA, li), X, 0, lane, [] {});
+        gemm<F16, HD / 16, FB, PB, ROWB, T::CKF, true>(acc, wq, rsW, fwdW(setFwdA, li), X, 0, lane, fwd_params);
       }
     }
     TS();
@@ -539,9 +589,8 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
     refresh();
     const bool last = li == L.L - 1;
     if (!last) {
-      float bv[8];
       for_blocks([&](int fb, int pb, int qp, int row) {
-        if (pb == 0) ld_params8(L.offB[li], ubase(fb, qp), bv);
+        const float (&bv)[8] = bvq[fb][qp];
         float a[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] = softplus_f(acc[fb][pb][8 * qp + e] + bv[e]);
@@ -550,12 +599,8 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
         else put_x(F16, fb, pb, qp, a, 0);
       });
     } else {
-      float bv[8], wv[8];
       for_blocks([&](int fb, int pb, int qp, int row) {
-        if (pb == 0) {
-          ld_params8(L.offB[li], ubase(fb, qp), bv);
-          ld_params8(L.offWout, ubase(fb, qp), wv);
-        }
+        const float (&bv)[8] = bvq[fb][qp], (&wv)[8] = wvq[fb][qp];
         float a[8], pl[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -589,11 +634,13 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
     TS();
     lds_barrier();
     TS();
-  }
+  };
+  fwd_layer(0, std::true_type{});
+  for (int li = 1; li < L.L; ++li) fwd_layer(li, std::false_type{});
   // sdf = (raw + noise) * so   (fc_map.py:104-109)
   float my_sdf = 0.f;
   if (tid < BM) {
-    float r = p.params[L.offBout];
+    float r = b_out;   // (requested by the prologue)
 #pragma unroll
     for (int k = 0; k < T::NW; ++k) r += part[(k * BM + tid) * 4];
     const int64_t n = n0 + tid;
@@ -914,6 +961,7 @@ __global__ __launch_bounds__(CHAIN_NW * 64, (HD <= 256 && EP == HD && !oper_x2_a
   TS();   // (loss sums written)
   // ------------------------------------------------------------------ Ebar = J_pe gbar  -> region 2 (bf16)
   if (tid < HD / 4) {   // w_out for the top epilogue (0 for the padding units of a narrower net: out of the descriptor's range)
+    // (requesting it behind the G gemm instead, next to the loss stage's inputs, measured nothing: profiles/r07_prologue_round_trips.txt)
     const u32x4 w4 = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(p.params + L.offWout, (uint32_t)L.H * 4u), tid * 16, 0, 0);
     const float4 wv4 = make_float4(__uint_as_float(w4[0]), __uint_as_float(w4[1]), __uint_as_float(w4[2]), __uint_as_float(w4[3]));
     ((float4*)part)[tid] = wv4;

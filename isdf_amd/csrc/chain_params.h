@@ -15,6 +15,8 @@ struct ChainParams {
   float noise_std; uint64_t noise_seed, noise_off;   // in-kernel Philox noise when noise == null
   const int32_t* n_valid;     // device: rays (points = n_valid*S); null -> n_points_host
   int64_t n_points_host;
+  int64_t pts_capacity;       // points the `pts` buffer holds (train: max_rays * S; forward only: n_points_host): what a workgroup may
+                              // request BEFORE it knows n_valid -- the tile's descriptor is clipped to it (chain.hip prologue)
   int32_t S;
   // per-ray inputs (train)
   const float* z_vals; const float* depth; const float* dirsC; const float* dirsW; const float* normals;
@@ -38,6 +40,8 @@ struct DwParams {
   const uint16_t* spill;
   const float* pe_aux;   // [nTiles*TILE_PTS][8], written by the chain kernel (ChainParams::pe_aux)
   const int32_t* n_valid; int64_t n_points_host; int32_t S;
+  int32_t cap_tiles;     // tiles the spill and pe_aux buffers hold (WorkspaceLayout::nTiles): a K-split's first tile is requested before
+                         // n_valid is known, through descriptors that are empty for a tile index at or beyond it (dw.hip prologue)
   float* dwPart;   // [dw_total_slabs][256*256] (isdf_common.h)
 };
 

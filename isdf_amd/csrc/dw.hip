@@ -77,6 +77,12 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
   static_assert(CH == 8 && BM / 16 == 4, "one 16-bit chunk rides behind each of the eight half-steps (an e4m3 chunk behind every other)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const NetLayout& L = p.lay;
+  // n_valid is REQUESTED here, in front of the unit decode, and first looked at in run(), behind the requests for the K-split's first
+  // tile: those depend on blockIdx alone, so the kernel opens with one memory round trip instead of two dependent ones in front of its
+  // 26 stages.  (Through a descriptor: the memory counter retires in order, so the wait for it leaves the tile's loads in flight;
+  // empty for a null n_valid.)
+  const int32_t nvRaw = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(make_rsrc(p.n_valid, p.n_valid ? 4u : 0u), 0, 0, 0);
+  asm volatile("" ::: "memory");   // (the request stays up here)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wo = w >> 1, wi = w & 1;               // this wave's 128 x 128 quadrant of the unit
   // block -> (unit, K-split): units have 35 or 40 splits (isdf_common.h)
@@ -95,8 +101,11 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
   // EP = 512 operand) is all zeros: no parameter sits behind any of its dW columns and the step tail never reads its slab.
   if (fromEmb && slBfull * DW_BLK >= L.E) return;
 
-  const int64_t P = p.n_valid ? (int64_t)(*p.n_valid) * p.S : p.n_points_host;
-  const int nTiles = (int)((P + TILE_PTS - 1) / TILE_PTS);
+  // The K-split's first tile is requested (run()) before the workgroup knows that the tile exists: through descriptors that are EMPTY
+  // when the tile index is at or beyond what the buffers hold (every load reads 0 and touches nothing).  A tile inside the buffers but
+  // beyond the valid points holds whatever an earlier step left there; its workgroup has no stage and uses nothing it loaded.
+  const bool tileInBuf = split < p.cap_tiles;
+  const uint32_t tileBytes = tileInBuf ? (uint32_t)p.sp.tileStride * 2u : 0u, auxBytes = tileInBuf ? (uint32_t)(BM * 32) : 0u;
 
   // stage q of tile t: q=0 -> (ZB[li], I), q=1 -> (P[li], GB).  Stage parity = q = register set = LDS buffer: the even stages'
   // operands are 16-bit tiles (8 x 16 B per thread and tensor), the odd stages' are e4m3 where the format says so (4 x 16 B;
@@ -115,7 +124,6 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-  const int nStages = split < nTiles ? 2 * ((nTiles - split + DW_SPLITK - 1) / DW_SPLITK) : 0;
   // a PE unit of a six-octave net builds its operand in the ALIGNED column order (see run()); others in the reference's order
   const bool peAligned = fromEmb && slBfull == 0 && L.E <= DW_BLK && L.n_freqs == 6;
 
@@ -227,8 +235,8 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
     // flat addresses the compiler keeps a 64-bit VGPR pair per chunk and tensor alive across the loop -- 48 registers this kernel
     // does not have.  A 16-bit tile slice: 8 chunks of 4 KB (frag16_piece: chunk c is 32 features = 256 pieces behind chunk 0), slices
     // 32 KB apart; an e4m3 slice: 4 chunks of 4 KB, slices 16 KB apart.
-    const int tileBytes = (int)p.sp.tileStride * 2;
-    auto tile_rsrc = [&](int64_t off, int t) { return make_rsrc(p.spill + off + (int64_t)t * p.sp.tileStride, (uint32_t)tileBytes); };
+    int nStages = 0;      // two per tile of this K-split; known behind the first tile's requests (below)
+    auto tile_rsrc = [&](int64_t off, int t) { return make_rsrc(p.spill + off + (int64_t)t * p.sp.tileStride, tileBytes); };
     auto issue0 = [&](int st, auto cTag) {        // even stage: ZB and the layer input, 16-bit
       constexpr int c = decltype(cTag)::value;
       const int t = split + (st >> 1) * DW_SPLITK;
@@ -244,7 +252,7 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
         if constexpr (g8) {
           if constexpr (h == 1) regB1[ks] = bload16<kAuxDwLoad>(tile_rsrc(offG, t), vo8, slB * 16384 + ks * 4096);
           if constexpr (ks == 3 && h == 1) {       // behind the LAST slice: the commit of the previous odd stage reads the old scales until then
-            const rsrc_t rx = make_rsrc(p.pe_aux + (int64_t)t * BM * 8, BM * 32);
+            const rsrc_t rx = make_rsrc(p.pe_aux + (int64_t)t * BM * 8, auxBytes);
             sG1[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (tid & 31) * 32 + 28, 0, 0));
             sG1[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (tid & 31) * 32 + 28, 32 * 32, 0));
           }
@@ -280,11 +288,11 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
         *(float4*)(smem + T::DIRTAB + tid * 16) = make_float4(kDirs[0][tid] * kInv2Pi, kDirs[1][tid] * kInv2Pi, kDirs[2][tid] * kInv2Pi, 0.f);
     }
     // pe_aux of the k-th tile of this workgroup: 64 points x 2 float4, one float4 per thread of the first two waves
-    auto load_aux = [&](int k) {          // (unconditional, as every load of the pipeline: threads 128.. load a row they do not store)
-      k = min(k, nStages / 2 - 1);
-      const uint4 v = bload16<0>(make_rsrc(p.pe_aux + (int64_t)(split + k * DW_SPLITK) * BM * 8, BM * 32), (tid & 127) * 16, 0);
+    auto load_aux_at = [&](int k) {       // (unconditional, as every load of the pipeline: threads 128.. load a row they do not store)
+      const uint4 v = bload16<0>(make_rsrc(p.pe_aux + (int64_t)(split + k * DW_SPLITK) * BM * 8, auxBytes), (tid & 127) * 16, 0);
       auxr = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     };
+    auto load_aux = [&](int k) { load_aux_at(min(k, nStages / 2 - 1)); };
     auto store_aux = [&](int k) {         // (threads 128.. hold and store the same rows again: no branch in the stage loop)
       *(float4*)(smem + 4 * T::TEN + (k & 1) * T::AUXB + (tid & 127) * 16) = auxr;
     };
@@ -443,8 +451,22 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
       fn(std::integral_constant<int, 3>{}, I0{}); fn(std::integral_constant<int, 3>{}, I1{});
     };
 
+    // The first tile's two stages (and a PE unit's first pe_aux rows) are requested BEFORE n_valid is looked at: their tile index
+    // is `split`.  Then the stage count; a K-split without a tile leaves with its zero accumulators (an exact zero slab).
+    if constexpr (PE) load_aux_at(0);
+    each_slice([&](auto k, auto h) { issue0(0, std::integral_constant<int, 2 * decltype(k)::value + decltype(h)::value>{}); });
+    each_slice([&](auto k, auto h) { issue1(1, k, h); });
+    {
+      int nv = nvRaw;
+      asm volatile("" : "+v"(nv) : : "memory");      // n_valid is consumed from here on: every request above stays in front of the wait for it
+      nv = __builtin_amdgcn_readfirstlane(nv);
+      const int64_t P = p.n_valid ? (int64_t)nv * p.S : p.n_points_host;
+      const int nTiles = (int)((P + TILE_PTS - 1) / TILE_PTS);
+      nStages = split < nTiles ? 2 * ((nTiles - split + DW_SPLITK - 1) / DW_SPLITK) : 0;
+    }
+    if (nStages == 0) return;
     if constexpr (PE) {
-      load_aux(0); store_aux(0); load_aux(1);
+      store_aux(0); load_aux(1);
       if constexpr (NFT != 0 && !ALIGNED && SLT == 1) {      // the zero padding behind the last cosine column: the same in every stage, written once into both buffers
         constexpr int c0 = 3 + 2 * N_DIRS * NFT - DW_BLK, npad = DW_BLK - c0;
         typedef typename Op<F16>::e eT0;
@@ -455,8 +477,6 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
         }
       }
     }
-    each_slice([&](auto k, auto h) { issue(0, std::false_type{}, k, h); });
-    each_slice([&](auto k, auto h) { issue(1, std::true_type{}, k, h); });
     if constexpr (PE) __syncthreads();          // tile 0's pe_aux rows are in LDS
     if constexpr (PE) fill_fetch(0, std::false_type{}, std::integral_constant<int, 0>{});
     each_slice([&](auto k, auto h) { commit(0, std::false_type{}, k, h); issue(2, std::false_type{}, k, h); });
@@ -488,8 +508,7 @@ __global__ __launch_bounds__(256, 1) void dw_kernel(const DwParams p) {
   typedef std::integral_constant<int, 0> I0_; typedef std::integral_constant<int, 1> I1_;
   // the reference-order fill at a compile-time octave count: the nine / eleven-octave nets (16-bit spills: SP8 = 0 instantiations only)
   const bool straightRef = SP8 == 0 && fromEmb && L.EP == 2 * DW_BLK && (L.n_freqs == 9 || L.n_freqs == 11);
-  if (nStages == 0) {}      // (more K-splits than tiles: a zero slab)
-  else if (fromEmb && peAligned) run(std::true_type{}, P8T{}, std::integral_constant<int, 6>{}, I0_{});
+  if (fromEmb && peAligned) run(std::true_type{}, P8T{}, std::integral_constant<int, 6>{}, I0_{});
   else if (straightRef) {
     if constexpr (SP8 == 0) {
       if (L.n_freqs == 9) { if (slBfull == 0) run(std::true_type{}, P8T{}, std::integral_constant<int, 9>{}, I0_{}); else run(std::true_type{}, P8T{}, std::integral_constant<int, 9>{}, I1_{}); }
