@@ -609,6 +609,29 @@ int isdf_slice_images(const float* pts, const float* sdf, int64_t n, const isdf_
 int isdf_plane_points(const float* origin, const float* du, const float* dv, int32_t H, int32_t W, float* pts_out,
                       void* stream);
 
+/* ---- visibility against posed depth frames ---------------------------------------
+ * "Is a world point in front of a posed depth frame, inside its image, and no more than trunc metres behind the surface?" --
+ * the use_projection=True branch of geometry.frustum.is_visible_torch (frustum.py:87-133), the project's one definition of the
+ * visible region (Trainer.eval_object_sdf, trainer.py:1976-1981; the masks of the slice figures, eval/figs/slices.py:274) -- for
+ * every pair of F frames and n points in ONE pass; nothing of size F * n is kept unless `mask` is asked for.
+ * T_CW is CAMERA-FROM-WORLD (the caller inverts its poses; the reference uses torch.linalg.inv).  Per pair, with a_rc the
+ * frame's matrix, every operation rounded to fp32, no fused multiply-add, IEEE division:
+ *   xc = ((a00*x + a01*y) + a02*z) + a03, yc and zc alike from rows 1 and 2 (row 3 is not read)
+ *   u = (fx*xc + cx*zc) / zc,  v = (fy*yc + cy*zc) / zc
+ *   inside  = u > 0 && u < (float)W && v > 0 && v < (float)H          (NaN and +-inf compare false)
+ *   pixel   = ((int)v, (int)u), truncated as .long() truncates
+ *   visible = inside && zc > 0 && zc < depth[f][row][col] + trunc     (a pixel of 0 or NaN has no case of its own)
+ * Equal to a numpy float32 model of these lines on every pair, and to the reference wherever float32 decides as float64 does.
+ * count [n] int32: the frames that see the point.  mask [F,n] u8 (optional): 1 where frame f sees point i.  n_seen (optional):
+ * one int64, the points with count > 0.  None needs initialisation, all are integers combined by integer adds: the same inputs
+ * give the same bytes.  n = 0 or F = 0 writes zeros and reads neither pts nor depth.  Up to two memsets and two launches on
+ * `stream` (one more launch per further 2^30 points), no workspace.
+ * ISDF_EINVAL: n < 0 or n > 2^38; F < 0; H or W < 1 or H * W > 2^31 - 1; F * n beyond int64; an intrinsic or trunc that is not
+ * finite; count NULL with n > 0; pts, T_CW or depth NULL with n > 0 and F > 0.                                              */
+int isdf_visible_points(const float* pts, int64_t n, const float* T_CW, const float* depth, int32_t F, int32_t H, int32_t W,
+                        float fx, float fy, float cx, float cy, float trunc, int32_t* count, uint8_t* mask, int64_t* n_seen,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ SYMBOLS = [
     "isdf_frame_avg", "isdf_adamw", "isdf_estimate_normals", "isdf_render_depth", "isdf_allreduce_sum_f32",
     "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables", "isdf_render_ws_bytes", "isdf_render_views",
     "isdf_sdf_metrics", "isdf_nn_distance", "isdf_slice_images", "isdf_plane_points", "isdf_region_metrics",
+    "isdf_visible_points",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -189,6 +190,7 @@ def lib():
     L.isdf_slice_images.argtypes = [vp, vp, i64, P(ColormapArgs), P(GtVolumeArgs), f32, f32, vp, vp, vp, vp, vp, vp]
     L.isdf_plane_points.argtypes = [P(f32), P(f32), P(f32), i32, i32, vp, vp]
     L.isdf_region_metrics.argtypes = [P(RegionArgs), vp, vp, i64, vp]
+    L.isdf_visible_points.argtypes = [vp, i64, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64

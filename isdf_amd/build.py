@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
-SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "slices.hip", "capi.hip"]
+SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "slices.hip", "visible.hip", "capi.hip"]
 HEADERS = ["isdf_common.h", "launchers.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
@@ -32,10 +32,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 # either (the trilinear blend asks for its fused multiply-adds by name).
 # slices.hip: four points per thread through the same colour rule and the same trilinear blend as eval.hip (one shared header,
 # one set of flags); its colour index, cost fields and plane points must equal fp32 models bit for bit.
+# visible.hip: eight frames' camera transforms of one point side by side, the point the shared operand of the same refused form; the
+# predicate must equal an fp32 model bit for bit (every operation rounded, no fused multiply-add).
 PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"],
             "dw.hip": ["-fno-slp-vectorize"], "mesh.hip": ["-fno-slp-vectorize"],
             "render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "eval.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
-            "slices.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
+            "slices.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "visible.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
 
 
 def _hipcc():

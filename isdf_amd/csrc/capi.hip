@@ -520,4 +520,17 @@ int isdf_plane_points(const float* origin, const float* du, const float* dv, int
   return launch_plane_points(origin, du, dv, H, W, pts_out, (hipStream_t)stream);
 }
 
+// ---- visibility against posed depth frames (visible.hip)
+int isdf_visible_points(const float* pts, int64_t n, const float* T_CW, const float* depth, int32_t F, int32_t H, int32_t W,
+                        float fx, float fy, float cx, float cy, float trunc, int32_t* count, uint8_t* mask, int64_t* n_seen,
+                        void* stream) {
+  isdf_clear_stale_hip_error();
+  if (n < 0 || n > ((int64_t)1 << 38) || F < 0 || H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff) return ISDF_EINVAL;
+  if (F > 0 && n > INT64_MAX / F) return ISDF_EINVAL;                      // the [F, n] mask is indexed in int64
+  for (float v : {fx, fy, cx, cy, trunc})
+    if (!__builtin_isfinite(v)) return ISDF_EINVAL;
+  if (n > 0 && (!count || (F > 0 && (!pts || !T_CW || !depth)))) return ISDF_EINVAL;
+  return launch_visible_points(pts, n, T_CW, depth, F, H, W, fx, fy, cx, cy, trunc, count, mask, n_seen, (hipStream_t)stream);
+}
+
 }  // extern "C"

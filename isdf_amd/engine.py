@@ -751,6 +751,29 @@ class Engine:
                    "isdf_nn_distance")
         return dist, index, total
 
+    def visible_points(self, pts, T_CW, depth, cam, trunc=0.2, want_mask=False):
+        """(count i32 [n], mask u8 [F,n] or None, n_seen i64 [1]) on the device: isdf_visible_points, the predicate of
+        geometry.frustum.is_visible_torch (frustum.py:87-133, use_projection=True) for every pair of the F posed depth frames and the
+        n points in one pass -- count[i] frames see point i, n_seen points are seen by at least one.  pts [n,3]; T_CW [F,4,4]
+        CAMERA-FROM-WORLD (isdf_amd.metrics.visible_points inverts T_WC); depth [F,H,W]; cam: anything with fx, fy, cx, cy.
+        No host synchronisation, and nothing of size F * n unless `want_mask`."""
+        if depth.dim() != 3:
+            raise ValueError("visible_points: depth must be [F, H, W] (got %s)" % (tuple(depth.shape),))
+        F, H, W = (int(v) for v in depth.shape)
+        p, T, d = self._flat(pts, torch.float32, 3), self._flat(T_CW, torch.float32, 16), self._flat(depth, torch.float32)
+        n = int(p.shape[0])
+        if int(T.shape[0]) != F:
+            raise ValueError("visible_points: %d poses for %d depth frames" % (T.shape[0], F))
+        count = torch.empty(n, dtype=torch.int32, device=self.device)
+        mask = torch.empty(F, n, dtype=torch.uint8, device=self.device) if want_mask else None
+        n_seen = torch.empty(1, dtype=torch.int64, device=self.device)
+        # an empty tensor has no address to hand over, and the call reads or writes none of them then
+        given = lambda t: _ffi.ptr(t) if t is not None and t.numel() else None
+        _ffi.check(self.lib.isdf_visible_points(given(p), n, given(T), given(d), F, H, W, float(cam.fx), float(cam.fy), float(cam.cx),
+                                                float(cam.cy), float(trunc), given(count), given(mask), _ffi.ptr(n_seen),
+                                                _stream(self.device)), "isdf_visible_points")
+        return count, mask, n_seen
+
     # ---- SDF slice images --------------------------------------------------------------
     def slice_images(self, pts, sdf, cmap=None, volume=None, chomp_eps=None, oob_fill=0.0):
         """(pred_rgb u8 [n,3], gt f32 [n], gt_rgb u8 [n,3], pred_cost f32 [n], gt_cost f32 [n]) on the device, None for what was

@@ -17,7 +17,8 @@ reference `isdf.modules.trainer.Trainer` INSTANCE to the HIP kernels behind the 
     Trainer.eval_sdf            trainer.py:1819-1866 (ground-truth lookup, mask, L1, bins and CHOMP differences: ONE isdf_sdf_metrics
                                                       pass over the device copy of gt_sdf_interp's grid, one copy of 24 doubles)
     Trainer.eval_sdf_visible    trainer.py:1868-1905 (the cached sequence stays resident on the device; only new frames are uploaded)
-    Trainer.eval_object_sdf     trainer.py:1955-2008 (resident frames; per visible object one isdf_sdf_metrics call)
+    Trainer.eval_object_sdf     trainer.py:1955-2008 (resident frames; visibility by one isdf_visible_points launch, its counts the
+                                only copy; per visible object one isdf_sdf_metrics call)
     Trainer.eval_traj_cost      trainer.py:2010-2052 (validity count and both CHOMP sums from one record)
     Trainer.eval_mesh           trainer.py:2054-2064 (accuracy / completion by isdf_nn_distance instead of two host KD-trees)
     Trainer.eval_fixed          trainer.py:2080-2088 (eval_pts.fixed_pts_eval, eval_pts.py:96-299: resident frames, ONE sampler launch

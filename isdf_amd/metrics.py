@@ -1,5 +1,5 @@
 """Evaluation of the map against ground truth on the device (include/isdf_hip.h: isdf_sdf_metrics, isdf_region_metrics,
-isdf_nn_distance).
+isdf_nn_distance, isdf_visible_points).
 
     GtVolume              the ground-truth SDF grid resident on the device (what the reference keeps behind a scipy
                           RegularGridInterpolator, sdf_util.py:174-180)
@@ -8,8 +8,11 @@ isdf_nn_distance).
     region_metrics        the per-region figures of eval_pts.fixed_pts_eval (eval_pts.py:96-299): av_l1, bins, CHOMP, av_cossim for
                           the vis and vox sets in one launch pair, one host copy
     accuracy_completion   metrics.accuracy / completion (metrics.py:48-59): mean nearest-neighbour distance both ways
+    visible_points        geometry.frustum.is_visible_torch (frustum.py:87-133): per point the number of posed depth frames that
+                          see it -- in front of the frame, inside its image, no more than trunc behind the surface -- in one launch
+                          over all frames, O(n) memory
 
-`engine` is an isdf_amd.engine.Engine (or anything with its sdf_metrics / nn_distance methods).
+`engine` is an isdf_amd.engine.Engine (or anything with its sdf_metrics / nn_distance / visible_points methods).
 """
 import os
 import types
@@ -153,6 +156,16 @@ def accuracy_completion(engine, gt_points, rec_points):
     return float(_ratio(sums[0], rec.shape[0])), float(_ratio(sums[1], gt.shape[0]))
 
 
+def visible_points(engine, pts, T_WC_batch, depth_batch, cam, trunc=0.2, want_mask=False):
+    """(count i32 [n], mask u8 [F,n] or None, n_seen i64 [1]), all on the device: what frustum.is_visible_torch(pts, T_WC_batch,
+    depth_batch, H, W, fx, fy, cx, cy, trunc) decides (frustum.py:87-133), as count = inside.sum(0), mask = inside (only with
+    want_mask) and n_seen = (count > 0).sum().  The poses are inverted on the device with torch.linalg.inv, as the reference inverts
+    them; then ONE isdf_visible_points call.  cam: anything with fx, fy, cx, cy; H and W are depth_batch's."""
+    T_WC = torch.as_tensor(T_WC_batch).to(device=engine.device, dtype=torch.float32).reshape(-1, 4, 4)
+    T_CW = torch.linalg.inv(T_WC) if T_WC.shape[0] else T_WC
+    return engine.visible_points(pts, T_CW, depth_batch, cam, trunc=trunc, want_mask=want_mask)
+
+
 class EvalMethods:
     """The trainer-level half (trainer.py:1819-2088): a base class of hot_path.HotPath; `self` is the grafted Trainer."""
 
@@ -262,8 +275,10 @@ class EvalMethods:
 
     def eval_object_sdf(self, samples=10000):
         """Per object the mean |sdf - gt| in a box around it, NaN while it is not visible (trainer.py:1955-2008).  The visibility
-        test is the reference's (100 random offsets per object, frustum.is_visible_torch) on the resident frames; per visible
-        object one isdf_sdf_metrics call that keeps zero-valued ground truth; the records come back in one copy."""
+        test is the reference's (100 random offsets per object against every resident frame, frustum.is_visible_torch's predicate)
+        as ONE isdf_visible_points launch whose 100 x n_objects counts are copied back -- an engine without visible_points gets the
+        reference's own function; per visible object one isdf_sdf_metrics call that keeps zero-valued ground truth; the records
+        come back in one copy."""
         errors = None
         if self.obj_bounds_file is not None:
             ref = self._hip.ref_module
@@ -273,9 +288,14 @@ class EvalMethods:
             extents = obj_bounds[:, 1] - obj_bounds[:, 0]
             pts = obj_bounds[:, 0] + offsets[:, None] * extents
             depth_batch, T_WC_batch = self._eval_frames()
-            visible = ref.geometry.frustum.is_visible_torch(pts.view(-1, 3), T_WC_batch, depth_batch, self.H, self.W, self.fx,
-                                                            self.fy, self.cx, self.cy, trunc=0.05)
-            visible = visible.detach().cpu().numpy().sum(axis=0) > 0
+            if getattr(self.engine, "visible_points", None) is not None:
+                # one launch over the resident frames; the 100 x n_objects counts are all that comes back
+                count, _, _ = visible_points(self.engine, pts.view(-1, 3), T_WC_batch, depth_batch, self, trunc=0.05)
+                visible = count.cpu().numpy() > 0
+            else:                                # an engine without the kernel: the reference's eager chain and its [F, N] mask
+                visible = ref.geometry.frustum.is_visible_torch(pts.view(-1, 3), T_WC_batch, depth_batch, self.H, self.W, self.fx,
+                                                                self.fy, self.cx, self.cy, trunc=0.05)
+                visible = visible.detach().cpu().numpy().sum(axis=0) > 0
             visible = visible.reshape(100, len(obj_bounds))
             visible = visible.sum(axis=0) / 100 > 0.5
             vol, records = self._gt_volume(), []
