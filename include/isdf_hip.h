@@ -632,6 +632,75 @@ int isdf_visible_points(const float* pts, int64_t n, const float* T_CW, const fl
                         float fx, float fy, float cx, float cy, float trunc, int32_t* count, uint8_t* mask, int64_t* n_seen,
                         void* stream);
 
+/* ---- narrow-band selection for surface extraction -----------------------------------
+ * Which points of a D0 x D1 x D2 lattice a scalar field has to be evaluated at so that isdf_marching_cubes of the result
+ * equals isdf_marching_cubes of the dense grid: coarse to fine, strides coarse, coarse / 2, ..., 2.  A cell of stride s has its
+ * corners on the stride-s lattice, the far ones clipped to the last index of each axis (ragged grids and grids smaller than one
+ * coarse cell work); with (di, dj, dk) its clipped extents and a_rc the affine (the identity without has_transform),
+ *   w_r = fma(a_r2, dk, fma(a_r1, dj, a_r0 * di)),   d = sqrt(fma(w_2, w_2, fma(w_1, w_1, w_0 * w_0)))        (fp32).
+ * A cell is KEPT iff a corner value is not finite, or its corners are not all on one side of level (inside iff value < level,
+ * as marching cubes has it), or max over the corners of |f - level| <= slack * d, compared in fp32.  Every cell of stride
+ * `coarse` is tested; the children (2c .. 2c + 1 per axis) of kept cells are tested at the next stride.  At the end every
+ * lattice point of [2c - 1, 2c + 3] per axis around a kept stride-2 cell c, clipped to the grid, is evaluated: the cell and
+ * the one-point halo that the central-difference normals of marching cubes read.  Everything else stays NaN, and marching
+ * cubes skips it.  If the field is L-Lipschitz in world units and slack >= L, no sign-changing cell is lost and the mesh is the
+ * dense one bit for bit.
+ *
+ * The caller drives the levels, since the field is evaluated in between (for the network: isdf_sdf_eval):
+ *   begin;  for s = coarse, ..., 2:  select(s) -> n, emit(s), values = field(points), update(s);
+ *   select(1) -> n, emit(1), values = field(points), update(1);  leaks.
+ * The volume marks "not evaluated" with one NaN bit pattern (0x7fe15df0); a field value with these very bits is stored as the
+ * default NaN.  No atomic decides a position and all counts are integer sums: two runs give the same bytes.  The workspace
+ * needs no initialisation; it carries the kept flags from level to level, so one workspace serves one volume at a time.
+ * Every call: ISDF_EINVAL for a NULL args / volume / counts, a dimension < 2 or D0*D1*D2 > 2^31 - 1, coarse not a power of two
+ * >= 2, slack negative or not finite, level or the affine not finite, a stride that is not a power of two in [1, coarse];
+ * ISDF_EWORKSPACE for a workspace that is NULL or too small.                                                              */
+typedef struct isdf_band_args {
+  int32_t D0, D1, D2;         /* lattice points per axis, volume[i][j][k] row-major          */
+  int32_t coarse;             /* coarsest stride, a power of two >= 2                        */
+  float level, slack;
+  int32_t has_transform;
+  int32_t reserved;
+  float index_to_world[12];   /* rows of the 3x4 affine (used iff has_transform)             */
+  const float* points;        /* optional device [D0*D1*D2][3]: emit gathers from it instead of applying the affine */
+} isdf_band_args;
+
+/* up(x) = x rounded up to 256, c_a(s) = ceil((D_a - 1) / s), nb = ceil(D0*D1*D2 / 256):
+ *   sum over s = 2, 4, ..., coarse of up(c_0(s) * c_1(s) * c_2(s))  +  up(8 * nb)  +  up(16 * nb)  +  256
+ * (the kept flags per stride, the per-block sums and their offsets).  ISDF_EINVAL for dims / coarse outside the bounds above. */
+int64_t isdf_band_ws_bytes(int32_t D0, int32_t D1, int32_t D2, int32_t coarse);
+
+/* volume [D0][D1][D2] <- "not evaluated" everywhere.  One launch. */
+int isdf_band_begin(const isdf_band_args* args, float* volume, void* stream);
+
+/* counts[0] (device int64[2]) <- the points stride `stride` needs that are not evaluated yet: the corners of its candidate cells,
+ * or for stride 1 the cells and halos of the kept stride-2 cells.  Two launches. */
+int isdf_band_select(const isdf_band_args* args, int32_t stride, const float* volume, int64_t* counts, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
+/* After select at the same stride with the volume unchanged, n = the count it reported: index_out [n] int32 <- the points'
+ * linear indices, ascending in the stride's lattice order; pts_out [n][3] <- their positions: points[index] if args->points,
+ * else per row r  fma(a_r2, k, fma(a_r1, j, fma(a_r0, i, a_r3)))  -- the chain of isdf_grid_points.  Nothing is written at
+ * or past n.  n = 0 is a no-op.  One launch. */
+int isdf_band_emit(const isdf_band_args* args, int32_t stride, const float* volume, int32_t* index_out, float* pts_out, int64_t n,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
+/* volume[index[t]] <- values[t] for t < n (indices outside the volume are ignored); then, stride > 1: every cell of the stride
+ * is tested, its kept flag stored, counts <- (candidates, kept).  Stride 1 only scatters; counts may be NULL.  Up to three
+ * launches. */
+int isdf_band_update(const isdf_band_args* args, int32_t stride, float* volume, const int32_t* index, const float* values, int64_t n,
+                     int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* counts[0] <- the unit cells with eight evaluated finite corners not all on one side of level that lie in no kept stride-2
+ * cell.  They are halo cells, marching cubes will mesh them, and they say the surface left the band: slack was too small.
+ * Two launches. */
+int isdf_band_leaks(const isdf_band_args* args, const float* volume, int64_t* counts, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+
+/* pts_out [D0*D1*D2][3] <- index_to_world (rows of a 3x4 affine, HOST memory, read before the call returns) applied to every
+ * lattice point with the chain documented at emit: the dense grid whose values the band's agree with bit for bit. */
+int isdf_grid_points(int32_t D0, int32_t D1, int32_t D2, const float* index_to_world, float* pts_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

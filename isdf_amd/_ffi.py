@@ -23,6 +23,8 @@ SYMBOLS = [
     "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables", "isdf_render_ws_bytes", "isdf_render_views",
     "isdf_sdf_metrics", "isdf_nn_distance", "isdf_slice_images", "isdf_plane_points", "isdf_region_metrics",
     "isdf_visible_points",
+    "isdf_band_ws_bytes", "isdf_band_begin", "isdf_band_select", "isdf_band_emit", "isdf_band_update", "isdf_band_leaks",
+    "isdf_grid_points",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -93,6 +95,13 @@ MAX_INLINE_FRAMES = 8
 class McArgs(C.Structure):
     _fields_ = [("volume", C.c_void_p), ("D0", C.c_int32), ("D1", C.c_int32), ("D2", C.c_int32), ("level", C.c_float),
                 ("has_transform", C.c_int32), ("index_to_world", C.c_float * 12)]
+
+
+class BandArgs(C.Structure):
+    """isdf_band_args"""
+    _fields_ = [("D0", C.c_int32), ("D1", C.c_int32), ("D2", C.c_int32), ("coarse", C.c_int32), ("level", C.c_float),
+                ("slack", C.c_float), ("has_transform", C.c_int32), ("reserved", C.c_int32), ("index_to_world", C.c_float * 12),
+                ("points", C.c_void_p)]
 
 
 RANGE_SCALAR, RANGE_DEPTH, RANGE_UPSAMPLE = 0, 1, 2
@@ -191,10 +200,18 @@ def lib():
     L.isdf_plane_points.argtypes = [P(f32), P(f32), P(f32), i32, i32, vp, vp]
     L.isdf_region_metrics.argtypes = [P(RegionArgs), vp, vp, i64, vp]
     L.isdf_visible_points.argtypes = [vp, i64, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp]
+    L.isdf_band_ws_bytes.argtypes = [i32, i32, i32, i32]
+    L.isdf_band_begin.argtypes = [P(BandArgs), vp, vp]
+    L.isdf_band_select.argtypes = [P(BandArgs), i32, vp, vp, vp, i64, vp]
+    L.isdf_band_emit.argtypes = [P(BandArgs), i32, vp, vp, vp, i64, vp, i64, vp]
+    L.isdf_band_update.argtypes = [P(BandArgs), i32, vp, vp, vp, i64, vp, vp, i64, vp]
+    L.isdf_band_leaks.argtypes = [P(BandArgs), vp, vp, vp, i64, vp]
+    L.isdf_grid_points.argtypes = [i32, i32, i32, P(f32), vp, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64
     L.isdf_render_ws_bytes.restype = i64
+    L.isdf_band_ws_bytes.restype = i64
     if L.isdf_abi_version() != ABI_VERSION:
         raise IsdfError("libisdf_hip.so ABI %d != binding ABI %d" % (L.isdf_abi_version(), ABI_VERSION))
     _lib = L

@@ -533,4 +533,72 @@ int isdf_visible_points(const float* pts, int64_t n, const float* T_CW, const fl
   return launch_visible_points(pts, n, T_CW, depth, F, H, W, fx, fy, cx, cy, trunc, count, mask, n_seen, (hipStream_t)stream);
 }
 
+// ---- narrow-band selection for surface extraction (band.hip)
+static bool band_args_ok(const isdf_band_args* a) {
+  if (!a || !mesh_dims_ok(a->D0, a->D1, a->D2)) return false;
+  if (a->coarse < 2 || (a->coarse & (a->coarse - 1)) != 0) return false;
+  if (!(a->slack >= 0.f) || !__builtin_isfinite(a->slack) || !__builtin_isfinite(a->level)) return false;
+  if (a->has_transform)
+    for (int q = 0; q < 12; ++q)
+      if (!__builtin_isfinite(a->index_to_world[q])) return false;
+  return true;
+}
+
+// a stride the hierarchy has: a power of two in [lo, coarse]
+static bool band_stride_ok(const isdf_band_args* a, int32_t stride, int32_t lo) {
+  return stride >= lo && stride <= a->coarse && (stride & (stride - 1)) == 0;
+}
+
+int64_t isdf_band_ws_bytes(int32_t D0, int32_t D1, int32_t D2, int32_t coarse) {
+  if (!mesh_dims_ok(D0, D1, D2) || coarse < 2 || (coarse & (coarse - 1)) != 0) return ISDF_EINVAL;
+  return band_ws_bytes(D0, D1, D2, coarse);
+}
+
+int isdf_band_begin(const isdf_band_args* a, float* volume, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!band_args_ok(a) || !volume) return ISDF_EINVAL;
+  return launch_band_fill(volume, (int64_t)a->D0 * a->D1 * a->D2, (hipStream_t)stream);
+}
+
+int isdf_band_select(const isdf_band_args* a, int32_t stride, const float* volume, int64_t* counts, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!band_args_ok(a) || !band_stride_ok(a, stride, 1) || !volume || !counts) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < band_ws_bytes(a->D0, a->D1, a->D2, a->coarse)) return ISDF_EWORKSPACE;
+  return launch_band_select(*a, stride, volume, counts, workspace, (hipStream_t)stream);
+}
+
+int isdf_band_emit(const isdf_band_args* a, int32_t stride, const float* volume, int32_t* index_out, float* pts_out, int64_t n,
+                   void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!band_args_ok(a) || !band_stride_ok(a, stride, 1) || !volume || n < 0) return ISDF_EINVAL;
+  if (n == 0) return ISDF_OK;
+  if (!index_out || !pts_out) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < band_ws_bytes(a->D0, a->D1, a->D2, a->coarse)) return ISDF_EWORKSPACE;
+  return launch_band_emit(*a, stride, volume, index_out, pts_out, n, workspace, (hipStream_t)stream);
+}
+
+int isdf_band_update(const isdf_band_args* a, int32_t stride, float* volume, const int32_t* index, const float* values, int64_t n,
+                     int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!band_args_ok(a) || !band_stride_ok(a, stride, 1) || !volume || n < 0 || (n > 0 && (!index || !values))) return ISDF_EINVAL;
+  if (stride > 1 && !counts) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < band_ws_bytes(a->D0, a->D1, a->D2, a->coarse)) return ISDF_EWORKSPACE;
+  return launch_band_update(*a, stride, volume, index, values, n, counts, workspace, (hipStream_t)stream);
+}
+
+int isdf_band_leaks(const isdf_band_args* a, const float* volume, int64_t* counts, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!band_args_ok(a) || !volume || !counts) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < band_ws_bytes(a->D0, a->D1, a->D2, a->coarse)) return ISDF_EWORKSPACE;
+  return launch_band_leaks(*a, volume, counts, workspace, (hipStream_t)stream);
+}
+
+int isdf_grid_points(int32_t D0, int32_t D1, int32_t D2, const float* index_to_world, float* pts_out, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!mesh_dims_ok(D0, D1, D2) || !index_to_world || !pts_out) return ISDF_EINVAL;
+  return launch_grid_points(D0, D1, D2, index_to_world, pts_out, (hipStream_t)stream);
+}
+
 }  // extern "C"

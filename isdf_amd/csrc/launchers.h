@@ -48,5 +48,14 @@ int launch_plane_points(const float* origin, const float* du, const float* dv, i
 int launch_visible_points(const float* pts, int64_t n, const float* T_CW, const float* depth, int32_t F, int32_t H, int32_t W,   // visible.hip
                           float fx, float fy, float cx, float cy, float trunc, int32_t* count, uint8_t* mask, int64_t* n_seen,
                           hipStream_t st);
+int64_t band_ws_bytes(int32_t D0, int32_t D1, int32_t D2, int32_t coarse);                                          // band.hip
+int launch_band_fill(float* vol, int64_t P, hipStream_t st);
+int launch_band_select(const isdf_band_args& a, int32_t stride, const float* vol, int64_t* counts, void* workspace, hipStream_t st);
+int launch_band_emit(const isdf_band_args& a, int32_t stride, const float* vol, int32_t* index_out, float* pts_out, int64_t n,
+                     void* workspace, hipStream_t st);
+int launch_band_update(const isdf_band_args& a, int32_t stride, float* vol, const int32_t* index, const float* values, int64_t n,
+                       int64_t* counts, void* workspace, hipStream_t st);
+int launch_band_leaks(const isdf_band_args& a, const float* vol, int64_t* counts, void* workspace, hipStream_t st);
+int launch_grid_points(int32_t D0, int32_t D1, int32_t D2, const float* A, float* pts_out, hipStream_t st);
 
 }  // namespace isdf

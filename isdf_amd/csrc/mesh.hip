@@ -13,6 +13,7 @@
 // between the passes.  Every workspace word is written before it is read in the same call: the workspace needs no zeroing.
 #include "isdf_common.h"
 #include "launchers.h"
+#include "block_scan.h"
 #include "mc_tables.h"
 
 namespace isdf {
@@ -77,31 +78,6 @@ __device__ inline int point_vertices(const float* __restrict__ v, const McGeom& 
   const float f0 = v[idx];
   return (int)edge_vertex(v, g, idx, i, j, k, 0, f0) + (int)edge_vertex(v, g, idx, i, j, k, 1, f0) +
          (int)edge_vertex(v, g, idx, i, j, k, 2, f0);
-}
-
-// block-wide exclusive scan of one int per thread (NT threads, wave64); *total = the block's sum
-template <int NT, typename T>
-__device__ inline T block_exclusive_scan(T x, T* lds, T* total) {
-  constexpr int NW = NT / 64;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T s = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(s, o, 64);
-    if (lane >= o) s += y;
-  }
-  if (lane == 63) lds[w] = s;
-  __syncthreads();
-  T off = 0, tot = 0;
-#pragma unroll
-  for (int q = 0; q < NW; ++q) {
-    const T b = lds[q];
-    off += q < w ? b : T(0);
-    tot += b;
-  }
-  __syncthreads();      // lds is free again for the caller's next scan
-  *total = tot;
-  return off + s - x;
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void mc_count_kernel(const float* __restrict__ vol, McGeom g, McWs ws) {

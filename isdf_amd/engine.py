@@ -223,6 +223,7 @@ class Engine:
         self._ws_ptr = self._params_ptr = self._shadow_ptr = None    # addresses train_step last set up for _launch_step
         self._fa_index_cache = {}     # host-side window -> its int32 device tensor (frame_avg)
         self._mesher = None       # marching-cubes workspace, count pair and output capacity (isdf_amd.mesh.Mesher)
+        self._band = None         # narrow-band workspace and count table (isdf_amd.mesh.BandSelector)
         self._renderer = None     # rendered-view workspace (isdf_amd.render.Renderer)
         self._eval_ws = None      # partial records of isdf_sdf_metrics
         self._region_ws = None    # ... and of isdf_region_metrics
@@ -642,6 +643,23 @@ class Engine:
             from .mesh import Mesher
             self._mesher = Mesher(self.device)
         return self._mesher(volume, level, index_to_world)
+
+    def band_volume(self, dims, index_to_world=None, points=None, level=0.0, slack=None, coarse=8, field=None):
+        """(volume [D0,D1,D2] f32, stats): `field` evaluated only in a narrow band around its `level` set, NaN elsewhere, so that
+        `marching_cubes(volume, level, index_to_world)` is the mesh of the dense grid (the isdf_band_* calls, include/isdf_hip.h:
+        coarse to fine over strides coarse .. 2, a cell kept iff a corner is not finite, its corners straddle level or all lie
+        within slack x its world diagonal of it).  With an L-Lipschitz field and slack >= L the mesh equals the dense one bit
+        for bit; `stats["leaks"]` > 0 says the surface left the band (isdf_amd.mesh.extract_surface then widens).
+
+        dims: D or (D0, D1, D2).  index_to_world: [3, 4] affine, measures the cells and (without `points`) makes the positions;
+        points: [D0*D1*D2, 3] device tensor to gather the positions from instead (a trainer's grid_pc).  field: callable, device
+        points [n, 3] -> values [n]; default `self.sdf_eval`.  slack: None = isdf_amd.mesh.DEFAULT_SLACK.
+        stats: levels = [dict(stride, candidates, kept, evaluated) per stride, dict(stride=1, evaluated) for the closing fill],
+        evaluated, dense (= D0*D1*D2), fraction, leaks, slack, coarse.  One small device -> host read per level."""
+        if self._band is None:
+            from .mesh import BandSelector
+            self._band = BandSelector(self.device)
+        return self._band(self.sdf_eval if field is None else field, dims, index_to_world, points, level, slack, coarse)
 
     # ---- rendered views ----------------------------------------------------------
     def render_views(self, T_WC, dirs_C, H, W, n_samples=0, **kw):
