@@ -701,6 +701,63 @@ int isdf_band_leaks(const isdf_band_args* args, const float* volume, int64_t* co
  * lattice point with the chain documented at emit: the dense grid whose values the band's agree with bit for bit. */
 int isdf_grid_points(int32_t D0, int32_t D1, int32_t D2, const float* index_to_world, float* pts_out, void* stream);
 
+/* ---- frame-to-map pose alignment ---------------------------------------------------
+ * One linearisation of "where was this depth frame really taken?" against the map: the depth pixels of a posed frame are
+ * back-projected under the pose guess, the caller evaluates its field (sdf and d sdf / dx, e.g. isdf_sdf_eval) at those world
+ * points, and the point-to-SDF residuals, their SE(3) Jacobians and the 6 x 6 normal equations are summed per pose.  Reference:
+ * none (the reference takes its poses from a tracker or from robot kinematics and never corrects them).
+ *
+ * Pixel lattice of a pose: every stride-th row and column from 0: n_pix = ceil(H / stride) * ceil(W / stride) pixels, row-major.
+ * B poses per call; pose b reads depth frame frame_of_pose[b], or frame b when frame_of_pose is NULL (then B <= F).
+ * A pixel is VALID iff its depth z is finite, != 0, >= min_depth and <= max_depth (max_depth may be +inf).
+ *
+ * Points (fp32, every operation rounded on its own, no fused multiply-add, IEEE division; c, r the pixel's column and row):
+ *   xc = (z * (c - cx)) / fx,  yc = (z * (r - cy)) / fy,  zc = z                       (pointcloud_from_depth_torch, transform.py:189-190)
+ *   x_w[i] = ((R[i][0]*xc + R[i][1]*yc) + R[i][2]*zc) + t[i]       with T_WC = [R | t], rows of 4
+ *   an invalid pixel gets t itself: finite, so the field call behind it is harmless, and the pixel is never counted.
+ *
+ * System (ALL arithmetic in double on the fp32 inputs widened; huber and trunc are fp32 and widened too): r = sdf; a point is USED
+ * iff its pixel is valid and |r| <= trunc; weight w = 1 if |r| <= huber, else huber / |r|; Huber cost rho = r^2 / 2 if |r| <= huber,
+ * else huber * (|r| - huber / 2); Jacobian J = [g, (x - t) x g] (g = grad, x the point): the twist (v, omega) about the camera
+ * centre under the update R <- exp(omega^) R, t <- t + v.  Per pose one record of ISDF_POSE_RECORD doubles:
+ *   [0] used points   [1] valid pixels   [2] sum w r^2   [3] sum rho   [4..9] sum w r J
+ *   [10..30] upper triangle of sum w J J^T, row-major ((0,0) .. (0,5), (1,1) .. (5,5))   [31] sum |r| over the used points
+ * Summed in a fixed order (per thread a grid-stride share in ascending order, lanes by shuffle, the four waves in wave order, one
+ * partial record per block, the blocks in block order) on a grid that depends on n_pix alone: a pose's record repeats bit for bit
+ * from run to run and does not depend on which other poses share the call.
+ *
+ * T_WC [B][12] (rows of the 3 x 4 pose) and frame_of_pose [B] are HOST arrays, read and checked before the call returns; they
+ * travel to the kernels as launch arguments.  Every call: ISDF_EINVAL for a NULL args / depth / T_WC / output / input, B, F, H, W
+ * or stride < 1, B > ISDF_POSE_MAX_POSES, H * W > 2^31 - 1, an intrinsic that is not finite, fx or fy == 0, min_depth > max_depth
+ * (or either NaN), a pose entry that is not finite, a frame_of_pose entry outside [0, F), B > F without frame_of_pose; the
+ * system also for huber or trunc <= 0 or not finite.  ISDF_EWORKSPACE for a workspace that is NULL or too small.  Nothing is
+ * launched by a refused call.                                                                                          */
+typedef struct isdf_pose_args {
+  int32_t B, F, H, W;            /* poses; depth frames and their size                          */
+  int32_t stride, reserved;      /* pixel lattice step (>= 1)                                   */
+  float fx, fy, cx, cy;
+  float min_depth, max_depth;
+  const float* depth;            /* device [F][H][W]                                            */
+  const float* T_WC;             /* HOST [B][12]                                                */
+  const int32_t* frame_of_pose;  /* HOST [B], or NULL: pose b reads frame b                     */
+} isdf_pose_args;
+
+#define ISDF_POSE_RECORD 32
+#define ISDF_POSE_MAX_BLOCKS 64       /* partial records per pose                               */
+#define ISDF_POSE_MAX_POSES 65536
+
+/* workspace bytes of the system call for B poses: B * ISDF_POSE_MAX_BLOCKS * ISDF_POSE_RECORD * 8 (ISDF_EINVAL for B outside
+ * [1, ISDF_POSE_MAX_POSES]).  No initialisation needed. */
+int64_t isdf_pose_ws_bytes(int32_t B);
+
+/* pts_out [B * n_pix][3] <- the world point of every lattice pixel of every pose.  One launch per 32 poses. */
+int isdf_pose_points(const isdf_pose_args* args, float* pts_out, void* stream);
+
+/* records [B][ISDF_POSE_RECORD] (device doubles) <- the sums above from pts [B * n_pix][3], sdf [B * n_pix], grad [B * n_pix][3]
+ * (device fp32; validity is re-derived from the depth).  One launch per 32 poses and one closing launch. */
+int isdf_pose_system(const isdf_pose_args* args, const float* pts, const float* sdf, const float* grad, float huber, float trunc,
+                     double* records, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ SYMBOLS = [
     "isdf_visible_points",
     "isdf_band_ws_bytes", "isdf_band_begin", "isdf_band_select", "isdf_band_emit", "isdf_band_update", "isdf_band_leaks",
     "isdf_grid_points",
+    "isdf_pose_ws_bytes", "isdf_pose_points", "isdf_pose_system",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -104,6 +105,14 @@ class BandArgs(C.Structure):
                 ("points", C.c_void_p)]
 
 
+class PoseArgs(C.Structure):
+    """isdf_pose_args (T_WC and frame_of_pose are HOST arrays)"""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("stride", C.c_int32),
+                ("reserved", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("depth", C.c_void_p), ("T_WC", C.c_void_p),
+                ("frame_of_pose", C.c_void_p)]
+
+
 RANGE_SCALAR, RANGE_DEPTH, RANGE_UPSAMPLE = 0, 1, 2
 
 
@@ -135,6 +144,8 @@ METRICS_RECORD = 24                                   # ISDF_METRICS_RECORD (dou
 SDF_METRICS_WS_BYTES = 1024 * METRICS_RECORD * 8      # ISDF_SDF_METRICS_WS_BYTES
 REGION_RECORD = 27                                    # ISDF_REGION_RECORD (doubles per set; a call writes two)
 REGION_METRICS_WS_BYTES = 1024 * 2 * REGION_RECORD * 8    # ISDF_REGION_METRICS_WS_BYTES
+POSE_RECORD = 32                                      # ISDF_POSE_RECORD (doubles per pose)
+POSE_MAX_BLOCKS = 64                                  # ISDF_POSE_MAX_BLOCKS
 FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
 
 
@@ -207,11 +218,15 @@ def lib():
     L.isdf_band_update.argtypes = [P(BandArgs), i32, vp, vp, vp, i64, vp, vp, i64, vp]
     L.isdf_band_leaks.argtypes = [P(BandArgs), vp, vp, vp, i64, vp]
     L.isdf_grid_points.argtypes = [i32, i32, i32, P(f32), vp, vp]
+    L.isdf_pose_ws_bytes.argtypes = [i32]
+    L.isdf_pose_points.argtypes = [P(PoseArgs), vp, vp]
+    L.isdf_pose_system.argtypes = [P(PoseArgs), vp, vp, vp, f32, f32, vp, vp, i64, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64
     L.isdf_render_ws_bytes.restype = i64
     L.isdf_band_ws_bytes.restype = i64
+    L.isdf_pose_ws_bytes.restype = i64
     if L.isdf_abi_version() != ABI_VERSION:
         raise IsdfError("libisdf_hip.so ABI %d != binding ABI %d" % (L.isdf_abi_version(), ABI_VERSION))
     _lib = L

@@ -601,4 +601,52 @@ int isdf_grid_points(int32_t D0, int32_t D1, int32_t D2, const float* index_to_w
   return launch_grid_points(D0, D1, D2, index_to_world, pts_out, (hipStream_t)stream);
 }
 
+// ---- frame-to-map pose alignment (pose.hip)
+// everything of isdf_pose_args the host can check: sizes, intrinsics, depth limits, and the two host arrays entry by entry
+static bool pose_args_ok(const isdf_pose_args* a) {
+  if (!a || !a->depth || !a->T_WC) return false;
+  if (a->B < 1 || a->B > ISDF_POSE_MAX_POSES || a->F < 1 || a->H < 1 || a->W < 1 || a->stride < 1) return false;
+  if ((int64_t)a->H * a->W > 0x7fffffff) return false;
+  for (float v : {a->fx, a->fy, a->cx, a->cy})
+    if (!__builtin_isfinite(v)) return false;
+  if (a->fx == 0.f || a->fy == 0.f) return false;
+  if (!(a->min_depth <= a->max_depth)) return false;                    // also refuses a NaN limit
+  if (!a->frame_of_pose && a->B > a->F) return false;
+  for (int64_t q = 0; q < (int64_t)a->B * 12; ++q)
+    if (!__builtin_isfinite(a->T_WC[q])) return false;
+  if (a->frame_of_pose)
+    for (int32_t b = 0; b < a->B; ++b)
+      if (a->frame_of_pose[b] < 0 || a->frame_of_pose[b] >= a->F) return false;
+  return true;
+}
+
+// a stride beyond the image selects pixel (0, 0) alone, as the largest in-image stride does: the kernels' ceil(H / stride) then
+// never adds past INT_MAX
+static isdf_pose_args pose_clamped(const isdf_pose_args* a) {
+  isdf_pose_args c = *a;
+  const int32_t most = a->H > a->W ? a->H : a->W;
+  if (c.stride > most) c.stride = most;
+  return c;
+}
+
+int64_t isdf_pose_ws_bytes(int32_t B) {
+  if (B < 1 || B > ISDF_POSE_MAX_POSES) return ISDF_EINVAL;
+  return (int64_t)B * ISDF_POSE_MAX_BLOCKS * ISDF_POSE_RECORD * 8;
+}
+
+int isdf_pose_points(const isdf_pose_args* a, float* pts_out, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!pose_args_ok(a) || !pts_out) return ISDF_EINVAL;
+  return launch_pose_points(pose_clamped(a), pts_out, (hipStream_t)stream);
+}
+
+int isdf_pose_system(const isdf_pose_args* a, const float* pts, const float* sdf, const float* grad, float huber, float trunc,
+                     double* records, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!pose_args_ok(a) || !pts || !sdf || !grad || !records) return ISDF_EINVAL;
+  if (!(huber > 0.f) || !(trunc > 0.f) || !__builtin_isfinite(huber) || !__builtin_isfinite(trunc)) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_pose_ws_bytes(a->B)) return ISDF_EWORKSPACE;
+  return launch_pose_system(pose_clamped(a), pts, sdf, grad, huber, trunc, records, (double*)workspace, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -57,5 +57,8 @@ int launch_band_update(const isdf_band_args& a, int32_t stride, float* vol, cons
                        int64_t* counts, void* workspace, hipStream_t st);
 int launch_band_leaks(const isdf_band_args& a, const float* vol, int64_t* counts, void* workspace, hipStream_t st);
 int launch_grid_points(int32_t D0, int32_t D1, int32_t D2, const float* A, float* pts_out, hipStream_t st);
+int launch_pose_points(const isdf_pose_args& a, float* pts, hipStream_t st);                                        // pose.hip
+int launch_pose_system(const isdf_pose_args& a, const float* pts, const float* sdf, const float* grad, float huber, float trunc,
+                       double* records, double* part, hipStream_t st);
 
 }  // namespace isdf

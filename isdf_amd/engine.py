@@ -228,6 +228,7 @@ class Engine:
         self._eval_ws = None      # partial records of isdf_sdf_metrics
         self._region_ws = None    # ... and of isdf_region_metrics
         self._nn_ws = None        # keys and partial sums of isdf_nn_distance
+        self._pose_ws = None      # partial records of isdf_pose_system (callers without a workspace of their own)
         self.reduce_buf = None
         self.reduce_extra = 0
         self.reduce_floats = 0
@@ -791,6 +792,79 @@ class Engine:
                                                 float(cam.cy), float(trunc), given(count), given(mask), _ffi.ptr(n_seen),
                                                 _stream(self.device)), "isdf_visible_points")
         return count, mask, n_seen
+
+    # ---- frame-to-map pose alignment ---------------------------------------------------
+    def _pose_args(self, name, depth, T_WC, cam, frame_of_pose, stride, min_depth, max_depth):
+        """(isdf_pose_args, what it points to, B, n_pix): depth [F,H,W] on the device; T_WC [B,4,4] or [B,12] and frame_of_pose [B]
+        as HOST arrays (the call checks them entry by entry and hands them on as launch arguments)"""
+        if depth.dim() != 3:
+            raise ValueError("%s: depth must be [F, H, W] (got %s)" % (name, tuple(depth.shape)))
+        F, H, W = (int(v) for v in depth.shape)
+        d = self._flat(depth, torch.float32)
+        T = np.asarray(T_WC.detach().cpu() if torch.is_tensor(T_WC) else T_WC)
+        if T.shape[-2:] == (4, 4):
+            T = T.reshape(-1, 4, 4)[:, :3, :]
+        elif T.ndim == 0 or T.shape[-1] != 12:
+            raise ValueError("%s: T_WC must be [B, 4, 4] or [B, 12] (got %s)" % (name, T.shape))
+        T = np.ascontiguousarray(T.reshape(-1, 12), dtype=np.float32)
+        B = int(T.shape[0])
+        fop = None
+        if frame_of_pose is not None:
+            fop = np.ascontiguousarray(np.asarray(frame_of_pose.detach().cpu() if torch.is_tensor(frame_of_pose) else frame_of_pose)
+                                       .reshape(-1), dtype=np.int32)
+            if fop.size != B:
+                raise ValueError("%s: %d poses but %d frame indices" % (name, B, fop.size))
+        stride = int(stride)
+        a = _ffi.PoseArgs()
+        a.B, a.F, a.H, a.W, a.stride = B, F, H, W, stride
+        a.fx, a.fy, a.cx, a.cy = float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy)
+        a.min_depth, a.max_depth = float(min_depth), float(max_depth)
+        a.depth = d.data_ptr() if d.numel() else None
+        a.T_WC = T.ctypes.data if B else None
+        a.frame_of_pose = None if fop is None else fop.ctypes.data
+        n_pix = (-(-H // stride)) * (-(-W // stride)) if stride >= 1 else 0
+        return a, (d, T, fop), B, n_pix
+
+    def pose_points(self, depth, T_WC, cam, frame_of_pose=None, stride=4, min_depth=0.0, max_depth=float("inf")):
+        """pts [B * n_pix, 3] f32 on the device: isdf_pose_points, the world point of every stride-th pixel (rows and columns from 0,
+        n_pix = ceil(H / stride) * ceil(W / stride), row-major) of the B poses T_WC ([B,4,4] or [B,12], host or device; read on the
+        host), pose b against depth[frame_of_pose[b]] (None: depth[b]).  The back-projection of pointcloud_from_depth_torch
+        (transform.py:189-190) and the pose, every operation rounded to fp32; a pixel whose depth is not finite, 0, below min_depth or
+        above max_depth gets the camera centre.  cam: anything with fx, fy, cx, cy.  No host synchronisation."""
+        a, keep, B, n_pix = self._pose_args("pose_points", depth, T_WC, cam, frame_of_pose, stride, min_depth, max_depth)
+        pts = torch.empty(B * n_pix, 3, dtype=torch.float32, device=self.device)
+        _ffi.check(self.lib.isdf_pose_points(C.byref(a), _ffi.ptr(pts) if pts.numel() else None, _stream(self.device)),
+                   "isdf_pose_points")
+        return pts
+
+    def pose_system(self, depth, T_WC, cam, pts, sdf, grad, frame_of_pose=None, stride=4, min_depth=0.0, max_depth=float("inf"),
+                    huber=0.05, trunc=0.3, out=None, workspace=None):
+        """records f64 [B, 32] on the device: isdf_pose_system, per pose the sums of one Gauss-Newton linearisation of the
+        point-to-SDF residual r = sdf over the points of `pose_points` with the same arguments -- [0] used points (valid pixel and
+        |r| <= trunc), [1] valid pixels, [2] sum w r^2, [3] the Huber cost, [4..9] sum w r J, [10..30] the upper triangle of
+        sum w J J^T (row-major), [31] sum |r| -- with w the Huber weight and J = [grad, (x - t) x grad] (include/isdf_hip.h).  All in
+        double, summed in a fixed order: the same inputs give the same bytes, whatever else shares the call.  pts [B*n_pix,3],
+        sdf [B*n_pix], grad [B*n_pix,3]: device f32.  out: a contiguous float64 [B, 32] to write into; workspace: a uint8 device
+        tensor of isdf_pose_ws_bytes(B) or more (None: the engine keeps one).  No host synchronisation."""
+        a, keep, B, n_pix = self._pose_args("pose_system", depth, T_WC, cam, frame_of_pose, stride, min_depth, max_depth)
+        p, s, g = self._flat(pts, torch.float32, 3), self._flat(sdf, torch.float32), self._flat(grad, torch.float32, 3)
+        if not (int(p.shape[0]) == s.numel() == int(g.shape[0]) == B * n_pix):
+            raise ValueError("pose_system: %d poses x %d pixels need %d points, sdf values and gradients (got %d, %d, %d)"
+                             % (B, n_pix, B * n_pix, p.shape[0], s.numel(), g.shape[0]))
+        need = int(self.lib.isdf_pose_ws_bytes(B))
+        _ffi.check(min(need, 0), "isdf_pose_ws_bytes(%d)" % B)
+        if workspace is None:
+            if self._pose_ws is None or self._pose_ws.numel() < need:
+                self._pose_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            workspace = self._pose_ws
+        if out is None:
+            out = torch.empty(B, _ffi.POSE_RECORD, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != B * _ffi.POSE_RECORD or not out.is_contiguous():
+            raise ValueError("pose_system: out must be a contiguous float64 [%d, %d]" % (B, _ffi.POSE_RECORD))
+        _ffi.check(self.lib.isdf_pose_system(C.byref(a), _ffi.ptr(p), _ffi.ptr(s), _ffi.ptr(g), float(huber), float(trunc),
+                                             _ffi.ptr(out), _ffi.ptr(workspace), int(workspace.numel()), _stream(self.device)),
+                   "isdf_pose_system")
+        return out
 
     # ---- SDF slice images --------------------------------------------------------------
     def slice_images(self, pts, sdf, cmap=None, volume=None, chomp_eps=None, oob_fill=0.0):
