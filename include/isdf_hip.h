@@ -758,6 +758,79 @@ int isdf_pose_points(const isdf_pose_args* args, float* pts_out, void* stream);
 int isdf_pose_system(const isdf_pose_args* args, const float* pts, const float* sdf, const float* grad, float huber, float trunc,
                      double* records, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- planning against the map: batched trajectory optimisation -----------------------
+ * One iteration of covariant (CHOMP-style) gradient descent on B trajectories at once: the caller evaluates its field (sdf and
+ * d sdf / dx, e.g. isdf_sdf_eval) at the query points of the trajectories, and one launch turns those values into the cost, its
+ * gradient, the preconditioned step and the query points of the next iteration.  Reference: none (the reference scores a recorded
+ * camera path with metrics.chomp_cost, metrics.py:95-104; it never moves one).
+ *
+ * B trajectories of T waypoints x[b][t] (world frame, fp32); waypoints 0 and T-1 are fixed, 1 .. T-2 are INTERIOR.  The robot
+ * is S body spheres that translate with the waypoint: offset o_s, radius r_s.  No rotation, no kinematics.
+ *
+ * Query points (fp32, one add per coordinate): q[b][t][s] = x[b][t] + o_s, layout [B][T][S][3].
+ *
+ * Everything else in double on the fp32 inputs widened (eps, w_obs, w_smooth, eta, max_step, tol are fp32 and widened too),
+ * every operation rounded on its own, no fused multiply-add, products and sums in the order written:
+ *   sample (t, s), every t, s ascending: BAD iff sdf or one of the three grad values is not finite; a bad sample adds its number
+ *     of non-finite values to [8] and nothing else.  Otherwise clearance d = sdf - r_s and
+ *       d < 0:          c = -d + eps * 0.5              c' = -1
+ *       0 <= d <= eps:  c = ((d - eps) * (d - eps)) / (2 * eps)   c' = (d - eps) / eps
+ *       d > eps:        c = 0                           c' = 0                      (metrics.chomp_cost, as eval.hip restates it)
+ *   per waypoint: C_t = sum_s c, G_t = sum_s c' * g (g = grad), C_0 = C_{T-1} = 0
+ *   velocity, interior t: v_t = (x_{t+1} - x_{t-1}) * 0.5, sigma_t = sqrt((v0 v0 + v1 v1) + v2 v2), vh_t = v_t / sigma_t (0 where
+ *     sigma_t == 0; vh_0 = vh_{T-1} = 0)
+ *   F_obs = sum_{t=1}^{T-2} C_t * sigma_t          F_smooth = (0.5 * (T-1)) * sum_{t=0}^{T-2} |x_{t+1} - x_t|^2
+ *   gradient, interior t (the exact gradient of w_obs F_obs + w_smooth F_smooth in x_t; rows 0 and T-1 are 0):
+ *     grad_t = w_obs * (sigma_t * G_t + (C_{t-1} vh_{t-1} - C_{t+1} vh_{t+1}) * 0.5) + (w_smooth * (T-1)) * ((2 x_t - x_{t-1}) - x_{t+1})
+ *   step: Delta = -(1 / eta) K^-1 grad per coordinate, K = (T-1) tridiag(-1, 2, -1) over the n = T-2 interior waypoints, by the
+ *     closed-form inverse through two ordered prefix sums (i = 1 .. n):
+ *       P_i = sum_{j <= i} j grad_j,  Q_i = sum_{j > i} (n+1-j) grad_j  (j ascending / descending),
+ *       y_i = ((n+1-i) P_i + i Q_i) / (n+1),  Delta_i = -(y_i / (eta * (T-1)))
+ *     m = max_t sqrt((D0 D0 + D1 D1) + D2 D2); kappa = 1 if m <= max_step, else max_step / m (max_step may be +inf)
+ *     x_t <- (float)((double)x_t + kappa * Delta_t)
+ *
+ * State, one int32 per trajectory, in/out: 0 moving, 1 converged, 2 invalid.  On entry with state 0: a bad sample anywhere
+ * in the trajectory -> state 2, x untouched; else m < tol -> state 1, x untouched (a converged trajectory's record describes
+ * exactly the x it leaves); else the step is applied.  On entry with any other state: x is untouched bit for bit, the state is
+ * kept, the record is written with [6] = [7] = 0.
+ *
+ * Record, ISDF_TRAJ_RECORD doubles per trajectory:
+ *   [0] F_obs   [1] F_smooth   [2] min d over the samples that are not bad (+inf if none)   [3] samples with d < 0
+ *   [4] samples with d < eps   [5] sum_t |grad_t|^2   [6] m   [7] kappa as applied (0 where no step was taken)
+ *   [8] non-finite values among sdf and grad   [9] state after the call   [10] path length sum_t |x_{t+1} - x_t|   [11..15] 0
+ * Sums: thread k of 256 takes waypoints k, k + 256, .. in ascending order, lanes by shuffle, the four waves in wave order: an
+ * order that depends on T and S alone.  A trajectory's record and its new x repeat bit for bit from run to run and do not
+ * depend on which other trajectories share the call.  x must be finite (device data, not checked).
+ *
+ * offsets [S][3] and radii [S] are HOST arrays, read and checked before the call returns; they travel as launch arguments.
+ * Every call: ISDF_EINVAL for a NULL args / x / offsets / radii / output / input (state may be NULL for isdf_traj_points only),
+ * B outside [1, ISDF_TRAJ_MAX_TRAJ], T outside [3, ISDF_TRAJ_MAX_WAYPOINTS], S outside [1, ISDF_TRAJ_MAX_SPHERES],
+ * B * T * S > 2^31 - 1, an offset that is not finite, a radius that is negative or not finite; the step also for eps, eta or
+ * max_step <= 0 or NaN, eps or eta infinite, w_obs, w_smooth or tol negative or not finite.  Nothing is launched by a refused
+ * call.                                                                                                                */
+#define ISDF_TRAJ_RECORD 16
+#define ISDF_TRAJ_MAX_WAYPOINTS 1024
+#define ISDF_TRAJ_MAX_SPHERES 32
+#define ISDF_TRAJ_MAX_TRAJ 65536
+
+typedef struct isdf_traj_args {
+  int32_t B, T, S, reserved;
+  float eps, w_obs, w_smooth, eta, max_step, tol;
+  float* x;              /* device [B][T][3]; isdf_traj_step updates it in place */
+  int32_t* state;        /* device [B]; may be NULL for isdf_traj_points          */
+  const float* offsets;  /* HOST [S][3] */
+  const float* radii;    /* HOST [S]    */
+} isdf_traj_args;
+
+/* q_out [B][T][S][3] <- the query points of x.  One launch. */
+int isdf_traj_points(const isdf_traj_args* args, float* q_out, void* stream);
+
+/* One iteration from sdf [B][T][S] and grad [B][T][S][3] (device fp32) at the query points of x: records
+ * [B][ISDF_TRAJ_RECORD] (device doubles), grad_out [B][T][3] (device doubles, or NULL) <- grad, x and state updated in place,
+ * q_out (or NULL) <- the query points of the x the call leaves, for every trajectory, frozen ones included.  One launch. */
+int isdf_traj_step(const isdf_traj_args* args, const float* sdf, const float* grad, double* records, float* q_out, double* grad_out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

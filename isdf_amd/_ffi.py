@@ -26,6 +26,7 @@ SYMBOLS = [
     "isdf_band_ws_bytes", "isdf_band_begin", "isdf_band_select", "isdf_band_emit", "isdf_band_update", "isdf_band_leaks",
     "isdf_grid_points",
     "isdf_pose_ws_bytes", "isdf_pose_points", "isdf_pose_system",
+    "isdf_traj_points", "isdf_traj_step",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -113,6 +114,13 @@ class PoseArgs(C.Structure):
                 ("frame_of_pose", C.c_void_p)]
 
 
+class TrajArgs(C.Structure):
+    """isdf_traj_args (offsets and radii are HOST arrays)"""
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("S", C.c_int32), ("reserved", C.c_int32), ("eps", C.c_float),
+                ("w_obs", C.c_float), ("w_smooth", C.c_float), ("eta", C.c_float), ("max_step", C.c_float), ("tol", C.c_float),
+                ("x", C.c_void_p), ("state", C.c_void_p), ("offsets", C.c_void_p), ("radii", C.c_void_p)]
+
+
 RANGE_SCALAR, RANGE_DEPTH, RANGE_UPSAMPLE = 0, 1, 2
 
 
@@ -146,6 +154,8 @@ REGION_RECORD = 27                                    # ISDF_REGION_RECORD (doub
 REGION_METRICS_WS_BYTES = 1024 * 2 * REGION_RECORD * 8    # ISDF_REGION_METRICS_WS_BYTES
 POSE_RECORD = 32                                      # ISDF_POSE_RECORD (doubles per pose)
 POSE_MAX_BLOCKS = 64                                  # ISDF_POSE_MAX_BLOCKS
+TRAJ_RECORD = 16                                      # ISDF_TRAJ_RECORD (doubles per trajectory)
+TRAJ_MAX_WAYPOINTS, TRAJ_MAX_SPHERES, TRAJ_MAX_TRAJ = 1024, 32, 65536    # ISDF_TRAJ_MAX_*
 FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
 
 
@@ -221,6 +231,8 @@ def lib():
     L.isdf_pose_ws_bytes.argtypes = [i32]
     L.isdf_pose_points.argtypes = [P(PoseArgs), vp, vp]
     L.isdf_pose_system.argtypes = [P(PoseArgs), vp, vp, vp, f32, f32, vp, vp, i64, vp]
+    L.isdf_traj_points.argtypes = [P(TrajArgs), vp, vp]
+    L.isdf_traj_step.argtypes = [P(TrajArgs), vp, vp, vp, vp, vp, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64

@@ -649,4 +649,35 @@ int isdf_pose_system(const isdf_pose_args* a, const float* pts, const float* sdf
   return launch_pose_system(pose_clamped(a), pts, sdf, grad, huber, trunc, records, (double*)workspace, (hipStream_t)stream);
 }
 
+// ---- planning against the map (traj.hip)
+// everything of isdf_traj_args the host can check: the sizes and the two host arrays entry by entry
+static bool traj_args_ok(const isdf_traj_args* a) {
+  if (!a || !a->x || !a->offsets || !a->radii) return false;
+  if (a->B < 1 || a->B > ISDF_TRAJ_MAX_TRAJ || a->T < 3 || a->T > ISDF_TRAJ_MAX_WAYPOINTS || a->S < 1 || a->S > ISDF_TRAJ_MAX_SPHERES)
+    return false;
+  if ((int64_t)a->B * a->T * a->S > 0x7fffffff) return false;
+  for (int32_t q = 0; q < a->S * 3; ++q)
+    if (!__builtin_isfinite(a->offsets[q])) return false;
+  for (int32_t s = 0; s < a->S; ++s)
+    if (!(a->radii[s] >= 0.f) || !__builtin_isfinite(a->radii[s])) return false;
+  return true;
+}
+
+int isdf_traj_points(const isdf_traj_args* a, float* q_out, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!traj_args_ok(a) || !q_out) return ISDF_EINVAL;
+  return launch_traj_points(*a, q_out, (hipStream_t)stream);
+}
+
+int isdf_traj_step(const isdf_traj_args* a, const float* sdf, const float* grad, double* records, float* q_out, double* grad_out,
+                   void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!traj_args_ok(a) || !a->state || !sdf || !grad || !records) return ISDF_EINVAL;
+  if (!(a->eps > 0.f) || !(a->eta > 0.f) || !(a->max_step > 0.f)) return ISDF_EINVAL;                  // also refuses NaN
+  if (!__builtin_isfinite(a->eps) || !__builtin_isfinite(a->eta)) return ISDF_EINVAL;                   // max_step may be +inf
+  for (float v : {a->w_obs, a->w_smooth, a->tol})
+    if (!(v >= 0.f) || !__builtin_isfinite(v)) return ISDF_EINVAL;
+  return launch_traj_step(*a, sdf, grad, records, q_out, grad_out, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -60,5 +60,8 @@ int launch_grid_points(int32_t D0, int32_t D1, int32_t D2, const float* A, float
 int launch_pose_points(const isdf_pose_args& a, float* pts, hipStream_t st);                                        // pose.hip
 int launch_pose_system(const isdf_pose_args& a, const float* pts, const float* sdf, const float* grad, float huber, float trunc,
                        double* records, double* part, hipStream_t st);
+int launch_traj_points(const isdf_traj_args& a, float* q_out, hipStream_t st);                                       // traj.hip
+int launch_traj_step(const isdf_traj_args& a, const float* sdf, const float* grad, double* records, float* q_out, double* grad_out,
+                     hipStream_t st);
 
 }  // namespace isdf

@@ -866,6 +866,74 @@ class Engine:
                    "isdf_pose_system")
         return out
 
+    # ---- planning against the map ------------------------------------------------------
+    def _traj_args(self, name, x, offsets, radii):
+        """(isdf_traj_args, what it points to, B, T, S): x [B,T,3] f32 on the device, used where it lies (the step writes it);
+        offsets [S,3] and radii [S] (or a scalar) as HOST arrays, checked by the call and handed on as launch arguments"""
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[-1] != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("%s: x must be a contiguous float32 tensor [B, T, 3]" % name)
+        if x.device.type != self.device.type or (self.device.index is not None and x.device.index != self.device.index):
+            raise ValueError("%s: x is on %s, the engine on %s" % (name, x.device, self.device))
+        off = np.ascontiguousarray(np.asarray(offsets.detach().cpu() if torch.is_tensor(offsets) else offsets, dtype=np.float32))
+        if off.ndim != 2 or off.shape[1] != 3:
+            raise ValueError("%s: offsets must be [S, 3] (got %s)" % (name, off.shape))
+        S = int(off.shape[0])
+        rad = np.asarray(radii.detach().cpu() if torch.is_tensor(radii) else radii, dtype=np.float32)
+        rad = np.ascontiguousarray(np.broadcast_to(rad.reshape(-1), (S,)) if rad.size == 1 else rad.reshape(-1))
+        if rad.size != S:
+            raise ValueError("%s: %d offsets but %d radii" % (name, S, rad.size))
+        B, T = int(x.shape[0]), int(x.shape[1])
+        a = _ffi.TrajArgs()
+        a.B, a.T, a.S = B, T, S
+        a.x = x.data_ptr() if x.numel() else None
+        a.offsets = off.ctypes.data if S else None
+        a.radii = rad.ctypes.data if S else None
+        return a, (off, rad), B, T, S
+
+    def traj_points(self, x, offsets, radii=0.0):
+        """q [B*T*S, 3] f32 on the device: isdf_traj_points, the query points x[b][t] + offsets[s] (one fp32 add per coordinate,
+        layout [B][T][S]) of B trajectories of T waypoints whose body is S spheres.  x: contiguous float32 [B,T,3] on the device;
+        offsets [S,3], radii [S] or a scalar: host or device, read on the host.  No host synchronisation."""
+        a, keep, B, T, S = self._traj_args("traj_points", x, offsets, radii)
+        q = torch.empty(B * T * S, 3, dtype=torch.float32, device=self.device)
+        _ffi.check(self.lib.isdf_traj_points(C.byref(a), _ffi.ptr(q) if q.numel() else None, _stream(self.device)),
+                   "isdf_traj_points")
+        return q
+
+    def traj_step(self, x, state, offsets, radii, sdf, grad, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=8.0, max_step=0.05, tol=1e-5,
+                  out=None, q_out=None, want_grad=False):
+        """records f64 [B, 16] on the device (and the cost gradient f64 [B,T,3] with want_grad): isdf_traj_step, one iteration of
+        covariant gradient descent on B trajectories from the field values sdf [B*T*S] and gradients grad [B*T*S,3] (device f32)
+        at `traj_points(x, offsets, radii)`.  x (contiguous float32 [B,T,3]) and state (contiguous int32 [B]: 0 moving,
+        1 converged, 2 invalid) are MODIFIED IN PLACE: a moving trajectory takes the step -(1/eta) K^-1 grad, clamped to max_step
+        per waypoint, unless a field value is not finite (-> 2) or the step is below tol (-> 1); the others are left bit for
+        bit.  Record: [0] F_obs, [1] F_smooth, [2] least clearance, [3] samples in collision, [4] samples within eps, [5] |grad|^2,
+        [6] longest waypoint step, [7] the clamp factor applied, [8] non-finite field values, [9] state, [10] path length
+        (include/isdf_hip.h).  out: a contiguous float64 [B, 16] to write into; q_out: a contiguous float32 tensor of B*T*S*3
+        values that receives the query points of the x the call leaves -- the next field call's input.  One launch, summed
+        in a fixed order: the same inputs give the same bytes, whatever else shares the call.  No host synchronisation."""
+        a, keep, B, T, S = self._traj_args("traj_step", x, offsets, radii)
+        if not torch.is_tensor(state) or state.dtype != torch.int32 or state.numel() != B or not state.is_contiguous() \
+                or state.device != x.device:
+            raise ValueError("traj_step: state must be a contiguous int32 tensor [%d] on x's device" % B)
+        s, g = self._flat(sdf, torch.float32), self._flat(grad, torch.float32, 3)
+        n = B * T * S
+        if not (s.numel() == int(g.shape[0]) == n):
+            raise ValueError("traj_step: %d x %d x %d needs %d sdf values and gradients (got %d, %d)" % (B, T, S, n, s.numel(), g.shape[0]))
+        if out is None:
+            out = torch.empty(B, _ffi.TRAJ_RECORD, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != B * _ffi.TRAJ_RECORD or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("traj_step: out must be a contiguous float64 [%d, %d] on x's device" % (B, _ffi.TRAJ_RECORD))
+        if q_out is not None and (q_out.dtype != torch.float32 or q_out.numel() != n * 3 or not q_out.is_contiguous()
+                                  or q_out.device != x.device):
+            raise ValueError("traj_step: q_out must be a contiguous float32 tensor of %d x 3 values on x's device" % n)
+        gout = torch.empty(B, T, 3, dtype=torch.float64, device=self.device) if want_grad else None
+        a.state = state.data_ptr() if B else None
+        a.eps, a.w_obs, a.w_smooth, a.eta, a.max_step, a.tol = (float(v) for v in (eps, w_obs, w_smooth, eta, max_step, tol))
+        _ffi.check(self.lib.isdf_traj_step(C.byref(a), _ffi.ptr(s) if n else None, _ffi.ptr(g) if n else None, _ffi.ptr(out),
+                                           _ffi.ptr(q_out), _ffi.ptr(gout), _stream(self.device)), "isdf_traj_step")
+        return (out, gout) if want_grad else out
+
     # ---- SDF slice images --------------------------------------------------------------
     def slice_images(self, pts, sdf, cmap=None, volume=None, chomp_eps=None, oob_fill=0.0):
         """(pred_rgb u8 [n,3], gt f32 [n], gt_rgb u8 [n,3], pred_cost f32 [n], gt_cost f32 [n]) on the device, None for what was
