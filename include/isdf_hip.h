@@ -831,6 +831,72 @@ int isdf_traj_points(const isdf_traj_args* args, float* q_out, void* stream);
 int isdf_traj_step(const isdf_traj_args* args, const float* sdf, const float* grad, double* records, float* q_out, double* grad_out,
                    void* stream);
 
+/* ---- the voxel baseline: TSDF fusion and the exact Euclidean distance transform ------------
+ * What the map is compared with (eval/plot_utils.py:108-130 reads a "GPU fusion" result; the reference does not ship the fusion):
+ * the posed depth frames fused into a truncated signed distance volume, and the full-range field of an occupancy grid by two
+ * Euclidean distance transforms (datasets/sdf_util.py:371-385, sdf_from_occupancy).
+ *
+ * isdf_tsdf_integrate fuses F posed depth frames into a running (tsdf, weight) pair of fp32 volumes [nx][ny][nz], row-major, k
+ * fastest.  The caller owns both and zeroes them before the first call.  For voxel (i, j, k) and frames f = 0 .. F-1 IN INDEX
+ * ORDER, every operation rounded to fp32 and nothing fused (a = T_CW[f], camera-from-world, rows of 4):
+ *   x = ox + (float)i * sx                                          (y, z alike)
+ *   xc = ((a00*x + a01*y) + a02*z) + a03,  yc, zc alike             (the chain of isdf_visible_points)
+ *   u = (fx*xc + cx*zc) / zc,  v = (fy*yc + cy*zc) / zc             (IEEE division)
+ *   uc = u + 0.5f, vc = v + 0.5f                                    (nearest pixel: pixel c's ray passes through u = c)
+ *   inside = uc >= 0 && uc < (float)W && vc >= 0 && vc < (float)H && zc > 0        (NaN and +-inf compare false)
+ *   col = (int)uc, row = (int)vc;  d = depth[f][row][col]
+ *   ok = inside && d > min_depth && d < max_depth                   (a pixel of 0 or NaN: no measurement)
+ *   s = d - zc;  ok = ok && s >= -trunc                             (projective distance along z; occluded voxels are skipped)
+ *   t = s < trunc ? s : trunc
+ *   where ok:  tsdf = (tsdf*w + t) / (w + 1.0f);  w = fminf(w + 1.0f, max_weight)
+ * The order over the frames defines the result: a voxel's frames are never split over workgroups or combined by atomics, so F
+ * frames in one call equal the same frames in any sequence of calls, bit for bit, and two runs give the same bytes.  One launch;
+ * no workspace.  F = 0 is a no-op that reads nothing.
+ * ISDF_EINVAL: a NULL args / tsdf / weight (depth / T_CW too when F > 0), a side < 1 or nx*ny*nz > 2^31 - 1, F < 0, H or W < 1 or
+ * H*W > 2^31 - 1, a spacing that is not finite or <= 0, an origin or intrinsic that is not finite, trunc not finite or <= 0,
+ * max_weight < 1 or NaN (+inf is allowed), min_depth NaN or < 0.  max_depth may be +inf.  Nothing is launched by a refused call. */
+typedef struct isdf_tsdf_args {
+  int32_t nx, ny, nz;            /* voxels per axis                                             */
+  int32_t F, H, W;               /* depth frames and their size                                 */
+  float origin[3], spacing[3];   /* voxel (i, j, k) at origin + (i, j, k) * spacing             */
+  float fx, fy, cx, cy;
+  float trunc, max_weight;
+  float min_depth, max_depth;
+  const float* depth;            /* device [F][H][W]                                            */
+  const float* T_CW;             /* device [F][4][4], camera-from-world                         */
+  float* tsdf;                   /* device [nx][ny][nz], updated in place                       */
+  float* weight;                 /* device [nx][ny][nz], updated in place                       */
+} isdf_tsdf_args;
+
+int isdf_tsdf_integrate(const isdf_tsdf_args* args, void* stream);
+
+/* Exact squared Euclidean distance transform.  feature u8 [nx][ny][nz] (device); a voxel q is a FEATURE voxel iff
+ * (feature[q] != 0) != (invert != 0).  dist2[p] (device int32 [nx][ny][nz]) <- min over the feature voxels q of |p - q|^2 in voxel
+ * units, exact; ISDF_EDT_NONE where there is no feature voxel.  Three separable min-plus passes z, y, x:
+ *   out[p] = min over q of the line of  in[q] + (p - q)^2,  saturated at ISDF_EDT_NONE
+ * (in = 0 at a feature voxel and ISDF_EDT_NONE elsewhere for the first pass): integer arithmetic, so the result equals the brute
+ * force minimum over all feature voxels, and sqrt((double)dist2) is scipy.ndimage.distance_transform_edt of the complement bit for
+ * bit.  Three launches.  ISDF_EINVAL: a NULL feature / dist2, a side < 1 or > ISDF_EDT_MAX_SIDE.  ISDF_EWORKSPACE: a workspace that
+ * is NULL or smaller than isdf_edt_ws_bytes.  No initialisation needed.                                                       */
+#define ISDF_EDT_NONE 1073741824      /* 2^30 */
+#define ISDF_EDT_MAX_SIDE 1024
+
+/* 2 * up(4 * nx*ny*nz), up(x) = x rounded up to 256: two int32 volumes.  The transform passes through the first; the occupancy
+ * field keeps one of its two transforms in the first and passes both through the second.  ISDF_EINVAL for a side outside
+ * [1, ISDF_EDT_MAX_SIDE]. */
+int64_t isdf_edt_ws_bytes(int32_t nx, int32_t ny, int32_t nz);
+
+int isdf_distance_transform(const uint8_t* feature, int32_t nx, int32_t ny, int32_t nz, int32_t invert, int32_t* dist2,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
+/* sdf_from_occupancy (sdf_util.py:371-385): with a = dist2 to the nearest occupied voxel (occ != 0) and b = dist2 to the nearest
+ * free one, both by the transform above,
+ *   out[p] = (float)((sqrt((double)a) - sqrt((double)b)) * voxel)            (correctly rounded double square roots; device fp32)
+ * positive in free space.  No occupied voxel anywhere: +inf everywhere; no free voxel: -inf (the reference's result is
+ * meaningless there).  Seven launches.  ISDF_EINVAL as for the transform, and for a voxel that is not finite or <= 0. */
+int isdf_occupancy_sdf(const uint8_t* occ, int32_t nx, int32_t ny, int32_t nz, double voxel, float* out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

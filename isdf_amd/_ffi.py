@@ -27,6 +27,7 @@ SYMBOLS = [
     "isdf_grid_points",
     "isdf_pose_ws_bytes", "isdf_pose_points", "isdf_pose_system",
     "isdf_traj_points", "isdf_traj_step",
+    "isdf_tsdf_integrate", "isdf_edt_ws_bytes", "isdf_distance_transform", "isdf_occupancy_sdf",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -121,6 +122,14 @@ class TrajArgs(C.Structure):
                 ("x", C.c_void_p), ("state", C.c_void_p), ("offsets", C.c_void_p), ("radii", C.c_void_p)]
 
 
+class TsdfArgs(C.Structure):
+    """isdf_tsdf_args"""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("trunc", C.c_float), ("max_weight", C.c_float), ("min_depth", C.c_float),
+                ("max_depth", C.c_float), ("depth", C.c_void_p), ("T_CW", C.c_void_p), ("tsdf", C.c_void_p), ("weight", C.c_void_p)]
+
+
 RANGE_SCALAR, RANGE_DEPTH, RANGE_UPSAMPLE = 0, 1, 2
 
 
@@ -156,6 +165,7 @@ POSE_RECORD = 32                                      # ISDF_POSE_RECORD (double
 POSE_MAX_BLOCKS = 64                                  # ISDF_POSE_MAX_BLOCKS
 TRAJ_RECORD = 16                                      # ISDF_TRAJ_RECORD (doubles per trajectory)
 TRAJ_MAX_WAYPOINTS, TRAJ_MAX_SPHERES, TRAJ_MAX_TRAJ = 1024, 32, 65536    # ISDF_TRAJ_MAX_*
+EDT_NONE, EDT_MAX_SIDE = 1 << 30, 1024                # ISDF_EDT_NONE, ISDF_EDT_MAX_SIDE
 FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
 
 
@@ -233,12 +243,17 @@ def lib():
     L.isdf_pose_system.argtypes = [P(PoseArgs), vp, vp, vp, f32, f32, vp, vp, i64, vp]
     L.isdf_traj_points.argtypes = [P(TrajArgs), vp, vp]
     L.isdf_traj_step.argtypes = [P(TrajArgs), vp, vp, vp, vp, vp, vp]
+    L.isdf_tsdf_integrate.argtypes = [P(TsdfArgs), vp]
+    L.isdf_edt_ws_bytes.argtypes = [i32, i32, i32]
+    L.isdf_distance_transform.argtypes = [vp, i32, i32, i32, i32, vp, vp, i64, vp]
+    L.isdf_occupancy_sdf.argtypes = [vp, i32, i32, i32, C.c_double, vp, vp, i64, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64
     L.isdf_render_ws_bytes.restype = i64
     L.isdf_band_ws_bytes.restype = i64
     L.isdf_pose_ws_bytes.restype = i64
+    L.isdf_edt_ws_bytes.restype = i64
     if L.isdf_abi_version() != ABI_VERSION:
         raise IsdfError("libisdf_hip.so ABI %d != binding ABI %d" % (L.isdf_abi_version(), ABI_VERSION))
     _lib = L

@@ -680,4 +680,45 @@ int isdf_traj_step(const isdf_traj_args* a, const float* sdf, const float* grad,
   return launch_traj_step(*a, sdf, grad, records, q_out, grad_out, (hipStream_t)stream);
 }
 
+// ---- the voxel baseline: TSDF fusion and the distance transform (fusion.hip)
+int isdf_tsdf_integrate(const isdf_tsdf_args* a, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!a || !a->tsdf || !a->weight) return ISDF_EINVAL;
+  if (a->nx < 1 || a->ny < 1 || a->nz < 1 || (int64_t)a->nx * a->ny > 0x7fffffff || (int64_t)a->nx * a->ny * a->nz > 0x7fffffff)
+    return ISDF_EINVAL;
+  if (a->F < 0 || a->H < 1 || a->W < 1 || (int64_t)a->H * a->W > 0x7fffffff) return ISDF_EINVAL;
+  for (int k = 0; k < 3; ++k)
+    if (!(a->spacing[k] > 0.f) || !__builtin_isfinite(a->spacing[k]) || !__builtin_isfinite(a->origin[k])) return ISDF_EINVAL;
+  for (float v : {a->fx, a->fy, a->cx, a->cy})
+    if (!__builtin_isfinite(v)) return ISDF_EINVAL;
+  if (!(a->trunc > 0.f) || !__builtin_isfinite(a->trunc)) return ISDF_EINVAL;
+  if (!(a->max_weight >= 1.f) || !(a->min_depth >= 0.f)) return ISDF_EINVAL;     // also refuses NaN; max_weight may be +inf
+  if (a->F > 0 && (!a->depth || !a->T_CW)) return ISDF_EINVAL;
+  return launch_tsdf_integrate(*a, (hipStream_t)stream);
+}
+
+static bool edt_dims_ok(int32_t nx, int32_t ny, int32_t nz) {
+  return nx >= 1 && ny >= 1 && nz >= 1 && nx <= ISDF_EDT_MAX_SIDE && ny <= ISDF_EDT_MAX_SIDE && nz <= ISDF_EDT_MAX_SIDE;
+}
+
+int64_t isdf_edt_ws_bytes(int32_t nx, int32_t ny, int32_t nz) {
+  return edt_dims_ok(nx, ny, nz) ? 2 * edt_volume_bytes(nx, ny, nz) : ISDF_EINVAL;
+}
+
+int isdf_distance_transform(const uint8_t* feature, int32_t nx, int32_t ny, int32_t nz, int32_t invert, int32_t* dist2,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!feature || !dist2 || !edt_dims_ok(nx, ny, nz)) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_edt_ws_bytes(nx, ny, nz)) return ISDF_EWORKSPACE;
+  return launch_distance_transform(feature, nx, ny, nz, invert, dist2, (int32_t*)workspace, (hipStream_t)stream);
+}
+
+int isdf_occupancy_sdf(const uint8_t* occ, int32_t nx, int32_t ny, int32_t nz, double voxel, float* out, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!occ || !out || !edt_dims_ok(nx, ny, nz) || !(voxel > 0.0) || !__builtin_isfinite(voxel)) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_edt_ws_bytes(nx, ny, nz)) return ISDF_EWORKSPACE;
+  return launch_occupancy_sdf(occ, nx, ny, nz, voxel, out, workspace, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -229,6 +229,7 @@ class Engine:
         self._region_ws = None    # ... and of isdf_region_metrics
         self._nn_ws = None        # keys and partial sums of isdf_nn_distance
         self._pose_ws = None      # partial records of isdf_pose_system (callers without a workspace of their own)
+        self._edt_ws = None       # the two int32 volumes of isdf_distance_transform / isdf_occupancy_sdf
         self.reduce_buf = None
         self.reduce_extra = 0
         self.reduce_floats = 0
@@ -792,6 +793,79 @@ class Engine:
                                                 float(cam.cy), float(trunc), given(count), given(mask), _ffi.ptr(n_seen),
                                                 _stream(self.device)), "isdf_visible_points")
         return count, mask, n_seen
+
+    # ---- the voxel baseline: TSDF fusion and the distance transform -----------------------
+    def tsdf_integrate(self, tsdf, weight, depth, T_CW, cam, origin, spacing, trunc, max_weight=float("inf"), min_depth=0.0,
+                       max_depth=float("inf")):
+        """isdf_tsdf_integrate: the F posed depth frames fused, in index order, into the running pair `tsdf`, `weight` (contiguous
+        float32 [nx,ny,nz] on this device, updated IN PLACE; zero before the first call), voxel (i, j, k) at origin + (i, j, k) *
+        spacing.  depth [F,H,W]; T_CW [F,4,4] CAMERA-FROM-WORLD (isdf_amd.fusion.integrate inverts T_WC); cam: anything with fx,
+        fy, cx, cy.  Per voxel a fixed fp32 sequence (include/isdf_hip.h): F frames in one call equal the same frames in any
+        sequence of calls bit for bit.  Returns (tsdf, weight).  No host synchronisation."""
+        if depth.dim() != 3:
+            raise ValueError("tsdf_integrate: depth must be [F, H, W] (got %s)" % (tuple(depth.shape),))
+        for name, t in (("tsdf", tsdf), ("weight", weight)):
+            if t.dim() != 3 or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != self.device.type:
+                raise ValueError("tsdf_integrate: %s must be a contiguous float32 [nx, ny, nz] tensor on %s" % (name, self.device))
+        if tsdf.shape != weight.shape:
+            raise ValueError("tsdf_integrate: tsdf is %s, weight %s" % (tuple(tsdf.shape), tuple(weight.shape)))
+        F, H, W = (int(v) for v in depth.shape)
+        T, d = self._flat(T_CW, torch.float32, 16), self._flat(depth, torch.float32)
+        if int(T.shape[0]) != F:
+            raise ValueError("tsdf_integrate: %d poses for %d depth frames" % (T.shape[0], F))
+        a = _ffi.TsdfArgs()
+        a.nx, a.ny, a.nz = (int(v) for v in tsdf.shape)
+        a.F, a.H, a.W = F, H, W
+        a.origin[:] = [float(v) for v in np.asarray(origin, np.float64).reshape(3)]
+        a.spacing[:] = [float(v) for v in np.asarray(spacing, np.float64).reshape(3)]
+        a.fx, a.fy, a.cx, a.cy = float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy)
+        a.trunc, a.max_weight, a.min_depth, a.max_depth = float(trunc), float(max_weight), float(min_depth), float(max_depth)
+        # an empty tensor has no address to hand over, and the call reads none of them then
+        a.depth = d.data_ptr() if d.numel() else None
+        a.T_CW = T.data_ptr() if T.numel() else None
+        a.tsdf = tsdf.data_ptr() if tsdf.numel() else None
+        a.weight = weight.data_ptr() if weight.numel() else None
+        _ffi.check(self.lib.isdf_tsdf_integrate(C.byref(a), _stream(self.device)), "isdf_tsdf_integrate")
+        return tsdf, weight
+
+    def _edt_workspace(self, dims):
+        need = int(self.lib.isdf_edt_ws_bytes(*dims))
+        _ffi.check(min(need, 0), "isdf_edt_ws_bytes%s" % (dims,))
+        if self._edt_ws is None or self._edt_ws.numel() < need:
+            self._edt_ws = None                     # release before growing: the two never need to coexist
+            self._edt_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._edt_ws
+
+    def _edt_feature(self, name, feature):
+        if feature.dim() != 3 or min(feature.shape) < 1:
+            raise ValueError("%s: a [nx, ny, nz] grid with every side >= 1 is needed (got %s)" % (name, tuple(feature.shape)))
+        f = feature.detach()
+        f = (f != 0) if f.dtype != torch.uint8 else f
+        return f.to(device=self.device, dtype=torch.uint8).contiguous(), tuple(int(v) for v in feature.shape)
+
+    def distance_transform(self, feature, invert=False):
+        """dist2 int32 [nx,ny,nz] on the device: isdf_distance_transform, the exact squared Euclidean distance (voxel units) from
+        every voxel to the nearest voxel q with (feature[q] != 0) != invert; _ffi.EDT_NONE (2^30) where there is none.
+        sqrt(dist2) in float64 is scipy.ndimage.distance_transform_edt of the complement bit for bit.  Sides up to 1024.  The
+        workspace is kept across calls.  No host synchronisation."""
+        f, dims = self._edt_feature("distance_transform", feature)
+        ws = self._edt_workspace(dims)
+        out = torch.empty(dims, dtype=torch.int32, device=self.device)
+        _ffi.check(self.lib.isdf_distance_transform(_ffi.ptr(f), dims[0], dims[1], dims[2], int(bool(invert)), _ffi.ptr(out),
+                                                    _ffi.ptr(ws), int(ws.numel()), _stream(self.device)), "isdf_distance_transform")
+        return out
+
+    def occupancy_sdf(self, occ, voxel):
+        """sdf float32 [nx,ny,nz] on the device: isdf_occupancy_sdf, the reference's sdf_from_occupancy (sdf_util.py:371-385) --
+        (distance to the nearest occupied voxel - distance to the nearest free one) * voxel, positive in free space, from two
+        exact distance transforms and float64 square roots.  +inf everywhere without an occupied voxel, -inf without a free one.
+        The workspace is kept across calls.  No host synchronisation."""
+        f, dims = self._edt_feature("occupancy_sdf", occ)
+        ws = self._edt_workspace(dims)
+        out = torch.empty(dims, dtype=torch.float32, device=self.device)
+        _ffi.check(self.lib.isdf_occupancy_sdf(_ffi.ptr(f), dims[0], dims[1], dims[2], float(voxel), _ffi.ptr(out), _ffi.ptr(ws),
+                                               int(ws.numel()), _stream(self.device)), "isdf_occupancy_sdf")
+        return out
 
     # ---- frame-to-map pose alignment ---------------------------------------------------
     def _pose_args(self, name, depth, T_WC, cam, frame_of_pose, stride, min_depth, max_depth):
