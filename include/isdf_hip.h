@@ -897,6 +897,81 @@ int isdf_distance_transform(const uint8_t* feature, int32_t nx, int32_t ny, int3
 int isdf_occupancy_sdf(const uint8_t* occ, int32_t nx, int32_t ny, int32_t nz, double voxel, float* out, void* workspace,
                        int64_t workspace_bytes, void* stream);
 
+/* ---- ground truth from a triangle mesh: distance to the nearest triangle and generalised winding number -------------------
+ * What the reference builds offline with trimesh (datasets/sdf_util.py:388-457: voxelise, fill, two distance transforms), exact
+ * instead: for every query point the distance to the nearest triangle of the mesh, and the winding number of the mesh around the
+ * point, which gives the sign on open and non-manifold meshes as well as on closed ones.  Brute force over points x triangles.
+ *
+ * isdf_tri_pack gathers vertices [nv][3] f32 and faces [m][3] i32 (device) once into `packed`: S = m rounded up to ISDF_TRI_TILE
+ * slots of ISDF_TRI_SLOT_FLOATS floats, slot f for face f (ISDF_TRI_PACKED_BYTES(m) bytes, 16-byte aligned):
+ *   [0..2] a   [3] ab.ab   [4..6] ab = b - a   [7] ab.ac   [8..10] ac = c - a   [11] ac.ac   [12..14] b   [15] valid (1 or 0)
+ *   [16..18] c   [19] 0   [20..22] nh = n / sqrtf(n.n), three correctly rounded divisions (n below)   [23] 0
+ * with every dot product (x*x' + y*y') + z*z' in rounded fp32 operations.  `transform` (HOST, 12 floats, rows of 4, or NULL) maps
+ * every vertex first: x' = ((T00*x + T01*y) + T02*z) + T03, y', z' alike.  A face is SKIPPED -- its slot is all zero, and it
+ * contributes nothing to any distance or winding number -- if
+ *   an index lies outside [0, nv)  (tested before anything is read through it), or a (transformed) vertex coordinate is not
+ *   finite:                                                                                       counted in counts[0];
+ *   n.n is not > 0 in fp32, n = ab x ac = (aby*acz - abz*acy, abz*acx - abx*acz, abx*acy - aby*acx)   (zero area, a repeated
+ *   vertex):                                                                                      counted in counts[1].
+ * counts: device int32[2], zeroed by the call.  One launch.  m = 0 packs nothing.
+ * ISDF_EINVAL: a NULL counts, nv or m < 0 or > 2^30, a NULL vertices with nv > 0, a NULL faces or packed with m > 0, a transform
+ * entry that is not finite.  ISDF_EWORKSPACE: packed_bytes < ISDF_TRI_PACKED_BYTES(m).
+ *
+ * isdf_tri_distance: pts [n][3] f32 (device) against a packed mesh of m faces.  Per pair of a point p and a valid slot, every
+ * operation rounded to fp32 and nothing fused:
+ *   ap = p - a
+ *   d1 = (abx*apx + aby*apy) + abz*apz      d2 = (acx*apx + acy*apy) + acz*apz
+ *   d3 = d1 - ab.ab    d4 = d2 - ab.ac    d5 = d1 - ab.ac    d6 = d2 - ac.ac
+ *   vc = d1*d4 - d3*d2    vb = d5*d2 - d1*d6    va = d3*d6 - d5*d4    e43 = d4 - d3    e56 = d5 - d6
+ *   (den, nv, nw) = the FIRST line that applies of
+ *     d1 <= 0 && d2 <= 0                  (1, 0, 0)                   vertex a
+ *     d3 >= 0 && d4 <= d3                 (1, 1, 0)                   vertex b
+ *     vc < 0 && d1 >= 0 && d3 <= 0        (d1 - d3, d1, 0)            edge ab
+ *     d6 >= 0 && d5 <= d6                 (1, 0, 1)                   vertex c
+ *     vb < 0 && d2 >= 0 && d6 <= 0        (d2 - d6, 0, d2)            edge ac
+ *     va < 0 && e43 >= 0 && e56 >= 0      (e43 + e56, e56, e43)       edge bc
+ *     otherwise                           ((va + vb) + vc, vb, vc)    the face
+ *   r = __fdiv_rn(1, den)    v = nv*r    w = nw*r
+ *   on the face:  dn = (nhx*apx + nhy*apy) + nhz*apz     dist2 = dn*dn        (the distance to the plane: exactly |dn| and
+ *                 exactly 0 in the plane for an axis-aligned face, whose nh is a signed unit vector exactly)
+ *   elsewhere:    dx = apx - (abx*v + acx*w)   (dy, dz alike)      dist2 = (dx*dx + dy*dy) + dz*dz
+ * (the regions of Ericson, Real-Time Collision Detection 5.1.5, with d3 .. d6 from the packed dot products and the three edge
+ * tests strict, so that a projection ON an edge line stays with the face).  The winner is the
+ * minimum of dist2 over the valid slots, the LOWEST FACE INDEX on ties (the integer minimum of dist2's bits << 32 | index; a NaN
+ * dist2 never wins); then
+ *   dist = sqrtf(dist2), correctly rounded    index = the winner's face index    closest = a + (ab*v + ac*w), v and w recomputed as above
+ * No valid slot (or m = 0): dist = +inf, index = -1, closest = NaN, winding = 0.
+ * Winding number: per pair, with a, b, c the vertices minus the point, in rounded fp32 operations
+ *   |a| = __fsqrt_rn((ax*ax + ay*ay) + az*az), the hardware square root, within one ulp  (|b|, |c| alike)    a.b = (ax*bx + ay*by) + az*bz  (b.c, c.a alike)
+ *   det = (ax*(by*cz - bz*cy) + ay*(bz*cx - bx*cz)) + az*(bx*cy - by*cx)
+ *   omega = 2 * atan2f(det, ((|a|*|b|*|c| + a.b*|c|) + b.c*|a|) + c.a*|b|)
+ * summed in a double per point in face order, winding = (float)(sum / (4 pi)).  The faces are split into C(n, m) chunks of whole
+ * tiles -- with Q = ceil(n / 1024) and t = ceil(m / ISDF_TRI_TILE):  c = min(max(ceil(1024 / Q), 1), t, 65535)  (1 for n = 0),
+ * C = ceil(t / ceil(t / c))  (1 for m = 0) -- a function of n and m alone; a point's chunk sums are added in chunk order, so the
+ * winding number repeats bit for bit.  A NULL `winding` selects a kernel without the solid-angle arithmetic.
+ * A query point with a non-finite coordinate: dist, closest and winding NaN, index -1.
+ * dist, index, closest [n][3], winding: device, each may be NULL.  record: device double[ISDF_TRI_RECORD], required:
+ *   [0] sum of dist over the finite points   [1] their number   [2] the number of non-finite points   [3] the largest dist (0
+ *   without a finite point)
+ * per-block partials in a fixed order, combined in block order by one closing block: the record repeats bit for bit.
+ * Four launches at most.  workspace: isdf_tri_ws_bytes, no initialisation needed.
+ * ISDF_EINVAL: a NULL record, n or m < 0 or > 2^30, a NULL pts with n > 0, a NULL packed with m > 0.  ISDF_EWORKSPACE: a workspace
+ * that is NULL or too small. */
+#define ISDF_TRI_TILE 256
+#define ISDF_TRI_SLOT_FLOATS 24
+#define ISDF_TRI_RECORD 4
+#define ISDF_TRI_PACKED_BYTES(m) ((((int64_t)(m) + ISDF_TRI_TILE - 1) / ISDF_TRI_TILE) * ISDF_TRI_TILE * ISDF_TRI_SLOT_FLOATS * 4)
+
+int isdf_tri_pack(const float* vertices, int64_t nv, const int32_t* faces, int64_t m, const float* transform, float* packed,
+                  int64_t packed_bytes, int32_t* counts, void* stream);
+
+/* 8*n*(1 + C(n, m)) + 32*ceil(n / 256) + 256: one 64-bit key and C doubles per point, one partial record per 256 points.
+ * ISDF_EINVAL for n or m < 0 or > 2^30. */
+int64_t isdf_tri_ws_bytes(int64_t n, int64_t m);
+
+int isdf_tri_distance(const float* pts, int64_t n, const float* packed, int64_t m, float* dist, int32_t* index, float* closest,
+                      float* winding, double* record, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ SYMBOLS = [
     "isdf_pose_ws_bytes", "isdf_pose_points", "isdf_pose_system",
     "isdf_traj_points", "isdf_traj_step",
     "isdf_tsdf_integrate", "isdf_edt_ws_bytes", "isdf_distance_transform", "isdf_occupancy_sdf",
+    "isdf_tri_pack", "isdf_tri_ws_bytes", "isdf_tri_distance",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -166,12 +167,18 @@ POSE_MAX_BLOCKS = 64                                  # ISDF_POSE_MAX_BLOCKS
 TRAJ_RECORD = 16                                      # ISDF_TRAJ_RECORD (doubles per trajectory)
 TRAJ_MAX_WAYPOINTS, TRAJ_MAX_SPHERES, TRAJ_MAX_TRAJ = 1024, 32, 65536    # ISDF_TRAJ_MAX_*
 EDT_NONE, EDT_MAX_SIDE = 1 << 30, 1024                # ISDF_EDT_NONE, ISDF_EDT_MAX_SIDE
+TRI_TILE, TRI_SLOT_FLOATS, TRI_RECORD = 256, 24, 4   # ISDF_TRI_TILE, ISDF_TRI_SLOT_FLOATS, ISDF_TRI_RECORD (doubles)
 FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
 
 
 def nn_ws_bytes(n):
     """ISDF_NN_WS_BYTES(n)"""
     return 8 * int(n) + 8 * ((int(n) + 255) // 256) + 256
+
+
+def tri_packed_bytes(m):
+    """ISDF_TRI_PACKED_BYTES(m)"""
+    return (int(m) + TRI_TILE - 1) // TRI_TILE * TRI_TILE * TRI_SLOT_FLOATS * 4
 
 
 class IsdfError(RuntimeError):
@@ -247,6 +254,9 @@ def lib():
     L.isdf_edt_ws_bytes.argtypes = [i32, i32, i32]
     L.isdf_distance_transform.argtypes = [vp, i32, i32, i32, i32, vp, vp, i64, vp]
     L.isdf_occupancy_sdf.argtypes = [vp, i32, i32, i32, C.c_double, vp, vp, i64, vp]
+    L.isdf_tri_pack.argtypes = [vp, i64, vp, i64, P(f32), vp, i64, vp, vp]
+    L.isdf_tri_ws_bytes.argtypes = [i64, i64]
+    L.isdf_tri_distance.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64
@@ -254,6 +264,7 @@ def lib():
     L.isdf_band_ws_bytes.restype = i64
     L.isdf_pose_ws_bytes.restype = i64
     L.isdf_edt_ws_bytes.restype = i64
+    L.isdf_tri_ws_bytes.restype = i64
     if L.isdf_abi_version() != ABI_VERSION:
         raise IsdfError("libisdf_hip.so ABI %d != binding ABI %d" % (L.isdf_abi_version(), ABI_VERSION))
     _lib = L

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
-SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "fusion.hip", "capi.hip"]
+SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "fusion.hip", "tri.hip", "capi.hip"]
 HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
@@ -42,12 +42,15 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 # double terms a float64 model written in the same order.
 # fusion.hip: eight frames' camera transforms of one voxel side by side, visible.hip's shape and the refused form again; the fused
 # (tsdf, weight) pair must equal an fp32 model bit for bit (every operation rounded, no fused multiply-add).
+# tri.hip: four query points against one triangle, the triangle the shared operand of the same refused form; closest point, squared
+# distance and index must equal an fp32 model bit for bit (every operation rounded, no fused multiply-add).
 PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"],
             "dw.hip": ["-fno-slp-vectorize"], "mesh.hip": ["-fno-slp-vectorize"],
             "render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "eval.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "slices.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "visible.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "band.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "pose.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
-            "traj.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "fusion.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
+            "traj.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "fusion.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
+            "tri.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -721,4 +721,31 @@ int isdf_occupancy_sdf(const uint8_t* occ, int32_t nx, int32_t ny, int32_t nz, d
   return launch_occupancy_sdf(occ, nx, ny, nz, voxel, out, workspace, (hipStream_t)stream);
 }
 
+// ---- ground truth from a triangle mesh (tri.hip)
+static bool tri_size_ok(int64_t v) { return v >= 0 && v <= ((int64_t)1 << 30); }
+
+int isdf_tri_pack(const float* vertices, int64_t nv, const int32_t* faces, int64_t m, const float* transform, float* packed,
+                  int64_t packed_bytes, int32_t* counts, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!counts || !tri_size_ok(nv) || !tri_size_ok(m) || (nv > 0 && !vertices) || (m > 0 && (!faces || !packed))) return ISDF_EINVAL;
+  if (transform)
+    for (int k = 0; k < 12; ++k)
+      if (!__builtin_isfinite(transform[k])) return ISDF_EINVAL;
+  if (packed_bytes < ISDF_TRI_PACKED_BYTES(m)) return ISDF_EWORKSPACE;
+  return launch_tri_pack(vertices, nv, faces, m, transform, packed, counts, (hipStream_t)stream);
+}
+
+int64_t isdf_tri_ws_bytes(int64_t n, int64_t m) {
+  if (!tri_size_ok(n) || !tri_size_ok(m)) return ISDF_EINVAL;
+  return 8 * n * (1 + tri_splits(n, m)) + 32 * ((n + 255) / 256) + 256;
+}
+
+int isdf_tri_distance(const float* pts, int64_t n, const float* packed, int64_t m, float* dist, int32_t* index, float* closest,
+                      float* winding, double* record, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!record || !tri_size_ok(n) || !tri_size_ok(m) || (n > 0 && !pts) || (m > 0 && !packed)) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_tri_ws_bytes(n, m)) return ISDF_EWORKSPACE;
+  return launch_tri_distance(pts, n, packed, m, dist, index, closest, winding, record, workspace, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -68,5 +68,10 @@ int64_t edt_volume_bytes(int32_t nx, int32_t ny, int32_t nz);
 int launch_distance_transform(const uint8_t* feature, int32_t nx, int32_t ny, int32_t nz, int invert, int32_t* dist2, int32_t* scratch,
                               hipStream_t st);
 int launch_occupancy_sdf(const uint8_t* occ, int32_t nx, int32_t ny, int32_t nz, double voxel, float* out, void* ws, hipStream_t st);
+int64_t tri_splits(int64_t n, int64_t m);                                                                           // tri.hip
+int launch_tri_pack(const float* verts, int64_t nv, const int32_t* faces, int64_t m, const float* T, float* packed, int32_t* counts,
+                    hipStream_t st);
+int launch_tri_distance(const float* pts, int64_t n, const float* packed, int64_t m, float* dist, int32_t* index, float* closest,
+                        float* winding, double* record, void* workspace, hipStream_t st);
 
 }  // namespace isdf

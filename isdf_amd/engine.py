@@ -230,6 +230,7 @@ class Engine:
         self._nn_ws = None        # keys and partial sums of isdf_nn_distance
         self._pose_ws = None      # partial records of isdf_pose_system (callers without a workspace of their own)
         self._edt_ws = None       # the two int32 volumes of isdf_distance_transform / isdf_occupancy_sdf
+        self._tri_ws = None       # keys, winding partials and partial records of isdf_tri_distance
         self.reduce_buf = None
         self.reduce_extra = 0
         self.reduce_floats = 0
@@ -866,6 +867,63 @@ class Engine:
         _ffi.check(self.lib.isdf_occupancy_sdf(_ffi.ptr(f), dims[0], dims[1], dims[2], float(voxel), _ffi.ptr(out), _ffi.ptr(ws),
                                                int(ws.numel()), _stream(self.device)), "isdf_occupancy_sdf")
         return out
+
+    # ---- ground truth from a triangle mesh ------------------------------------------------
+    def tri_pack(self, vertices, faces, transform=None):
+        """(packed f32 [slots, 24], counts i32 [2], m) on the device: isdf_tri_pack, the mesh gathered once into the layout
+        isdf_tri_distance reads (include/isdf_hip.h), slot f for face f, padded to the kernel's tile.  vertices [nv,3]; faces
+        [m,3] (any integer type; values beyond int32 become -1, a bad index); transform: None or a [3,4] / [4,4] affine applied to
+        the vertices first.  counts[0]: faces skipped for an index outside [0, nv) or a non-finite vertex; counts[1]: faces skipped
+        for zero fp32 area.  No host synchronisation."""
+        v = self._flat(torch.as_tensor(vertices), torch.float32, 3)
+        f = torch.as_tensor(faces).detach().to(self.device)
+        if f.is_floating_point() or f.dtype == torch.bool:
+            raise ValueError("tri_pack: faces must be integers (got %s)" % f.dtype)
+        f = f.reshape(-1, 3)
+        if f.dtype != torch.int32:
+            f = torch.where((f < 0) | (f > 0x7fffffff), torch.full_like(f, -1), f).to(torch.int32)
+        f = f.contiguous()
+        nv, m = int(v.shape[0]), int(f.shape[0])
+        T = None
+        if transform is not None:
+            A = np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform, np.float32)
+            if A.shape not in ((3, 4), (4, 4)):
+                raise ValueError("tri_pack: transform must be [3, 4] or [4, 4] (got %s)" % (A.shape,))
+            T = (C.c_float * 12)(*[float(x) for x in A[:3].reshape(-1)])
+        nbytes = _ffi.tri_packed_bytes(m)
+        packed = torch.empty(nbytes // (4 * _ffi.TRI_SLOT_FLOATS), _ffi.TRI_SLOT_FLOATS, dtype=torch.float32, device=self.device)
+        counts = torch.empty(2, dtype=torch.int32, device=self.device)
+        given = lambda t: _ffi.ptr(t) if t.numel() else None
+        _ffi.check(self.lib.isdf_tri_pack(given(v), nv, given(f), m, T, given(packed), nbytes, _ffi.ptr(counts),
+                                          _stream(self.device)), "isdf_tri_pack")
+        return packed, counts, m
+
+    def tri_distance(self, packed, m, pts, want_index=False, want_closest=False, want_winding=False, want_dist=True):
+        """(dist [n] f32, index [n] i32, closest [n,3] f32, winding [n] f32, record f64 [4]) on the device, None for what was
+        not asked for: isdf_tri_distance, every point of `pts` [n,3] against the `m` faces of `packed` (tri_pack) -- the exact
+        distance to the nearest triangle by a fixed fp32 sequence (the lowest face index on ties), the nearest point, and the
+        generalised winding number of the mesh around the point.  record: sum of dist over the finite points, their number, the
+        number of non-finite points, the largest dist.  The workspace is kept across calls.  No host synchronisation."""
+        p = self._flat(torch.as_tensor(pts), torch.float32, 3)
+        n, m = int(p.shape[0]), int(m)
+        if packed.dtype != torch.float32 or not packed.is_contiguous() or packed.numel() * 4 < _ffi.tri_packed_bytes(m):
+            raise ValueError("tri_distance: packed must be the contiguous float32 tensor tri_pack returned for %d faces" % m)
+        need = int(self.lib.isdf_tri_ws_bytes(n, m))
+        _ffi.check(min(need, 0), "isdf_tri_ws_bytes(%d, %d)" % (n, m))
+        if self._tri_ws is None or self._tri_ws.numel() < need:
+            self._tri_ws = None                     # release before growing: the two never need to coexist
+            self._tri_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        dev = self.device
+        dist = torch.empty(n, dtype=torch.float32, device=dev) if want_dist else None
+        index = torch.empty(n, dtype=torch.int32, device=dev) if want_index else None
+        closest = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_closest else None
+        winding = torch.empty(n, dtype=torch.float32, device=dev) if want_winding else None
+        record = torch.empty(_ffi.TRI_RECORD, dtype=torch.float64, device=dev)
+        given = lambda t: _ffi.ptr(t) if t is not None and t.numel() else None
+        _ffi.check(self.lib.isdf_tri_distance(given(p), n, given(packed) if m else None, m, given(dist), given(index),
+                                              given(closest), given(winding), _ffi.ptr(record), _ffi.ptr(self._tri_ws),
+                                              int(self._tri_ws.numel()), _stream(dev)), "isdf_tri_distance")
+        return dist, index, closest, winding, record
 
     # ---- frame-to-map pose alignment ---------------------------------------------------
     def _pose_args(self, name, depth, T_WC, cam, frame_of_pose, stride, min_depth, max_depth):

@@ -146,3 +146,54 @@ def keyframes(n, cam, seed=1, stride=40, noise_std=0.0):
 
 REPLICA_CAM = dict(H=680, W=1200, fx=600.0, fy=600.0, cx=599.5, cy=339.5)   # replicaCAD.json:10-17
 SCANNET_CAM = dict(H=480, W=640, fx=577.87, fy=577.87, cx=319.5, cy=239.5)
+
+
+def _box_mesh(lo, hi, inward):
+    """8 corners (index = x + 2 y + 4 z bits) and 12 triangles of an axis-aligned box, normals outward (or `inward`)"""
+    v = np.array([[(lo, hi)[(i >> k) & 1][k] for k in range(3)] for i in range(8)], np.float64)
+    quads = [(0, 4, 6, 2), (1, 3, 7, 5), (0, 1, 5, 4), (2, 6, 7, 3), (0, 2, 3, 1), (4, 5, 7, 6)]
+    f = np.array([t for p, q, r, s in quads for t in ((p, q, r), (p, r, s))], np.int32)
+    return v, (f[:, [0, 2, 1]] if inward else f)
+
+
+def _icosphere(centre, radius, subdiv):
+    """an icosahedron subdivided `subdiv` times, every vertex on the sphere, normals outward: 20 * 4^subdiv triangles"""
+    t = (1.0 + np.sqrt(5.0)) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1),
+         (-t, 0, -1), (-t, 0, 1)]
+    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(subdiv)):
+        mid = {}
+
+        def midpoint(i, j):
+            key = (min(i, j), max(i, j))
+            if key not in mid:
+                p = v[i] + v[j]
+                v.append(p / np.linalg.norm(p))
+                mid[key] = len(v) - 1
+            return mid[key]
+        g = []
+        for a, b, c in f:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            g += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = g
+    return np.asarray(centre, np.float64) + radius * np.array(v), np.array(f, np.int32)
+
+
+def room_mesh(subdiv=3, spheres=True):
+    """(vertices float64 [nv,3], faces int32 [m,3]): the analytic room as a triangle mesh whose every normal points into free
+    space -- the room box with its faces turned inward (12 triangles), the two floor boxes (24; faces 0..35 and vertices 0..23
+    are these three boxes) and, with `spheres`, three icospheres at subdivision `subdiv`: 36 + 3 * 20 * 4^subdiv triangles.
+    Each part is a closed surface of its own.  The generalised winding number is -1 in free space and 0 inside a solid or
+    outside the room; the distance to the mesh is |gt_sdf| inside the room up to the spheres' tessellation sag."""
+    parts = [_box_mesh(ROOM_LO, ROOM_HI, True)] + [_box_mesh(lo, hi, False) for lo, hi in BOXES]
+    if spheres:
+        parts += [_icosphere(c, r, subdiv) for c, r in SPHERES]
+    verts, faces, base = [], [], 0
+    for v, f in parts:
+        verts.append(v)
+        faces.append(f + base)
+        base += len(v)
+    return np.concatenate(verts), np.concatenate(faces).astype(np.int32)
