@@ -11,8 +11,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
-SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "fusion.hip", "tri.hip", "capi.hip"]
-HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
+SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "fusion.hip", "tri.hip", "capi.hip"]
+HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "block_reduce.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
 
@@ -30,6 +30,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 # eval.hip: the nearest-neighbour loop holds four queries against one target; vectorised, the shared target becomes the
 # broadcast operand of the same refused form; its squared distances must equal an fp32 model bit for bit, so no contraction
 # either (the trilinear blend asks for its fused multiply-adds by name).
+# reduce.hip: the closing launch of eval.hip's records (and tri.hip's), built as they are.
 # slices.hip: four points per thread through the same colour rule and the same trilinear blend as eval.hip (one shared header,
 # one set of flags); its colour index, cost fields and plane points must equal fp32 models bit for bit.
 # visible.hip: eight frames' camera transforms of one point side by side, the point the shared operand of the same refused form; the
@@ -47,6 +48,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"],
             "dw.hip": ["-fno-slp-vectorize"], "mesh.hip": ["-fno-slp-vectorize"],
             "render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "eval.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
+            "reduce.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "slices.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "visible.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "band.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "pose.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "traj.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "fusion.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],

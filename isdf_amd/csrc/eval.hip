@@ -5,11 +5,13 @@
 //   metrics.binned_losses                         isdf/eval/metrics.py:133-158
 //   metrics.chomp_cost                            isdf/eval/metrics.py:95-104
 //   metrics.accuracy / completion                 isdf/eval/metrics.py:48-59        (nearest-neighbour distances, brute force)
-// Both reductions are deterministic: per-block partial sums in double, combined in block order by one closing block; the
-// nearest neighbour is a minimum over integer keys (squared distance bits, then index), which no order can change.
+// Both reductions are deterministic: per-block partial sums in double (block_reduce.h), combined in block order by one closing
+// block (reduce.hip); the nearest neighbour is a minimum over integer keys (squared distance bits, then index), which no order can
+// change.
 #include "isdf_common.h"
 #include "launchers.h"
 #include "gt_volume_dev.h"
+#include "block_reduce.h"
 
 namespace isdf {
 
@@ -22,13 +24,6 @@ __device__ __forceinline__ double chomp(double s, double e) {
   if (s > 0.0) c = (1.0 / (2.0 * e)) * (s - e) * (s - e);
   if (s > e) c = 0.0;
   return c;
-}
-
-// sum over the 256 threads of a block in a fixed order: lanes by shuffle, then the four waves in wave order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
 }
 
 // One thread per point (grid-stride): grid coordinate, in-bounds test with the faces inclusive, trilinear value (all three
@@ -73,32 +68,7 @@ __global__ __launch_bounds__(256) void sdf_metrics_kernel(const isdf_gt_volume v
       }
     }
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int v = 0; v < REC; ++v) {
-    const double t = wave_sum(acc[v]);
-    if (lane == 0) sh[wave][v] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < REC)
-    part[(int64_t)blockIdx.x * REC + threadIdx.x] =
-        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-}
-
-// closing block: out[v] = sum over the nPart partial records, each thread a strided share in ascending order, then the block's
-// fixed-order sum (width values per record)
-__global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restrict__ part, int64_t nPart, int width,
-                                                           double* __restrict__ out) {
-  __shared__ double sh[4];
-  for (int v = 0; v < width; ++v) {
-    double t = 0.0;
-    for (int64_t b = threadIdx.x; b < nPart; b += 256) t += part[b * width + v];
-    t = wave_sum(t);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) out[v] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-  }
+  block_record_sum(acc, sh, part + (int64_t)blockIdx.x * REC);
 }
 
 // ---- region metrics (eval_pts.fixed_pts_eval, eval_pts.py:96-299) -------------------------------------------------------
@@ -117,11 +87,9 @@ __device__ __forceinline__ double grad_lookup(const isdf_gt_volume& vol, const i
 __global__ __launch_bounds__(256) void region_metrics_kernel(const isdf_gt_volume vol, const isdf_region_args a, int has_vol,
                                                              double* __restrict__ part) {
   __shared__ double sh[4][2 * RREC];
-  double acc[2][RREC];
+  double acc[2 * RREC];                   // set k's entry v at k * RREC + v, as in the record
 #pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int v = 0; v < RREC; ++v) acc[k][v] = 0.0;
+  for (int v = 0; v < 2 * RREC; ++v) acc[v] = 0.0;
   const float* __restrict__ pts = a.pts;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
     const unsigned f = (a.flags ? a.flags[i] : 3u) & (a.grad_sets ? 15u : 3u);
@@ -177,23 +145,12 @@ __global__ __launch_bounds__(256) void region_metrics_kernel(const isdf_gt_volum
     for (int k = 0; k < 2; ++k) {
       const bool in_sdf = (f >> k) & 1u, in_grad = (f >> (2 + k)) & 1u;
 #pragma unroll
-      for (int v = 0; v < 24; ++v) acc[k][v] += in_sdf ? c[v] : 0.0;
+      for (int v = 0; v < 24; ++v) acc[k * RREC + v] += in_sdf ? c[v] : 0.0;
 #pragma unroll
-      for (int v = 24; v < RREC; ++v) acc[k][v] += in_grad ? c[v] : 0.0;
+      for (int v = 24; v < RREC; ++v) acc[k * RREC + v] += in_grad ? c[v] : 0.0;
     }
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int v = 0; v < RREC; ++v) {
-      const double t = wave_sum(acc[k][v]);
-      if (lane == 0) sh[wave][k * RREC + v] = t;
-    }
-  __syncthreads();
-  if (threadIdx.x < 2 * RREC)
-    part[(int64_t)blockIdx.x * (2 * RREC) + threadIdx.x] =
-        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+  block_record_sum(acc, sh, part + (int64_t)blockIdx.x * (2 * RREC));
 }
 
 int launch_region_metrics(const isdf_region_args& a, double* records, double* part, hipStream_t st) {
@@ -207,8 +164,7 @@ int launch_region_metrics(const isdf_region_args& a, double* records, double* pa
     const int rc = isdf_launch_status();
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, part, blocks, 2 * RREC, records);
-  return isdf_launch_status();
+  return launch_reduce_partials(part, blocks, 2 * RREC, 0, records, st);
 }
 
 // ---- nearest neighbour, brute force -----------------------------------------------------------------------------------
@@ -282,20 +238,17 @@ __global__ __launch_bounds__(256) void nn_kernel(const float* __restrict__ query
 __global__ __launch_bounds__(256) void nn_finish_kernel(const unsigned long long* __restrict__ keys, int64_t n,
                                                         float* __restrict__ dist, int32_t* __restrict__ index,
                                                         double* __restrict__ part) {
-  __shared__ double sh[4];
+  __shared__ double sh[4][1];
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  double d = 0.0;
+  double d[1] = {0.0};
   if (q < n) {
     const unsigned long long k = keys[q];
     const float r = __fsqrt_rn(__uint_as_float((uint32_t)(k >> 32)));
     if (dist) dist[q] = r;
     if (index) index[q] = (int32_t)(uint32_t)k;
-    d = (double)r;
+    d[0] = (double)r;
   }
-  d = wave_sum(d);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = d;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  block_record_sum(d, sh, part + blockIdx.x);
 }
 
 int launch_sdf_metrics(const isdf_gt_volume& vol, const float* pts, const float* sdf, int64_t n, int exclude_zero,
@@ -309,8 +262,7 @@ int launch_sdf_metrics(const isdf_gt_volume& vol, const float* pts, const float*
     const int rc = isdf_launch_status();
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, part, blocks, REC, record);
-  return isdf_launch_status();
+  return launch_reduce_partials(part, blocks, REC, 0, record, st);
 }
 
 int launch_nn_distance(const float* query, int64_t n, const float* target, int64_t m, float* dist, int32_t* index,
@@ -342,8 +294,7 @@ int launch_nn_distance(const float* query, int64_t n, const float* target, int64
     hipLaunchKernelGGL(nn_finish_kernel, dim3((unsigned)fin), dim3(256), 0, st, keys, n, dist, index, part);
     if ((rc = isdf_launch_status())) return rc;
   }
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, part, fin, 1, dist_sum);
-  return isdf_launch_status();
+  return launch_reduce_partials(part, fin, 1, 0, dist_sum, st);
 }
 
 }  // namespace isdf

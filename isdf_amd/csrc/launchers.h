@@ -45,6 +45,7 @@ int launch_slice_images(const isdf_colormap* cmap, const isdf_gt_volume* vol, co
                         float* gt_cost, hipStream_t st);
 int launch_plane_points(const float* origin, const float* du, const float* dv, int32_t H, int32_t W, float* pts_out,
                         hipStream_t st);
+int launch_reduce_partials(const double* part, int64_t nPart, int width, uint64_t max_mask, double* out, hipStream_t st);   // reduce.hip
 int launch_visible_points(const float* pts, int64_t n, const float* T_CW, const float* depth, int32_t F, int32_t H, int32_t W,   // visible.hip
                           float fx, float fy, float cx, float cy, float trunc, int32_t* count, uint8_t* mask, int64_t* n_seen,
                           hipStream_t st);

@@ -5,7 +5,7 @@
 //                        built with -ffp-contract=off, build.py), so the points equal a numpy float32 model bit for bit
 //   pose_system_kernel   per pose the record of include/isdf_hip.h (counts, costs, sum w r J, upper triangle of sum w J J^T), all
 //                        in double on the fp32 inputs widened, reduced like eval.hip's records: a grid-stride share per thread,
-//                        lanes by shuffle, the four waves in wave order, one partial record per block
+//                        then block_reduce.h's order, one partial record per block
 //   pose_close_kernel    a pose's partial records in block order
 // The grid is (blocks per pose, poses of the chunk) with blocks per pose a function of n_pix alone, capped at ISDF_POSE_MAX_BLOCKS:
 // a pose's record does not depend on the run or on its neighbours in the call.  Poses and frame indices come from the host and
@@ -14,6 +14,7 @@
 // two kernels; the 32 accumulators are indexed statically throughout (64 VGPRs, nothing in scratch).
 #include "isdf_common.h"
 #include "launchers.h"
+#include "block_reduce.h"
 
 namespace isdf {
 
@@ -63,12 +64,6 @@ __global__ __launch_bounds__(256) void pose_points_kernel(const PoseCam cam, con
   }
 }
 
-__device__ __forceinline__ double pose_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // block (x, y): the grid-stride share x of pose pose0 + y; its partial record goes to part[pose][x]
 __global__ __launch_bounds__(256) void pose_system_kernel(const PoseCam cam, const PoseChunk chunk, int64_t pose0,
                                                           const float* __restrict__ pts, const float* __restrict__ sdf,
@@ -109,16 +104,7 @@ __global__ __launch_bounds__(256) void pose_system_kernel(const PoseCam cam, con
       }
     }
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int v = 0; v < PREC; ++v) {
-    const double t = pose_wave_sum(acc[v]);
-    if (lane == 0) sh[wave][v] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < PREC)
-    part[(pose * ISDF_POSE_MAX_BLOCKS + blockIdx.x) * PREC + threadIdx.x] =
-        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+  block_record_sum(acc, sh, part + (pose * ISDF_POSE_MAX_BLOCKS + blockIdx.x) * PREC);
 }
 
 // block = pose, thread v < PREC: records[pose][v] = its nPart partial records in block order

@@ -17,6 +17,7 @@
 // Nothing is indexed dynamically in registers: no scratch.
 #include "isdf_common.h"
 #include "launchers.h"
+#include "block_reduce.h"
 
 namespace isdf {
 
@@ -41,22 +42,6 @@ __global__ __launch_bounds__(256) void traj_points_kernel(const float* __restric
   const int s = (int)(i - bt * S);
 #pragma unroll
   for (int k = 0; k < 3; ++k) q[i * 3 + k] = x[bt * 3 + k] + body.off[s][k];
-}
-
-__device__ __forceinline__ double traj_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double traj_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double traj_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  return v;
 }
 
 __device__ __forceinline__ double traj_norm(double a, double b, double c) { return sqrt((a * a + b * b) + c * c); }
@@ -154,15 +139,17 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
 
   const int wave = tid >> 6, lane = tid & 63;
   {
-    const double v0 = traj_wave_sum(f_obs), v1 = traj_wave_sum(seg2), v2 = traj_wave_min(mind), v3 = traj_wave_sum(n_neg),
-                 v4 = traj_wave_sum(n_act), v5 = traj_wave_sum(gsq), v6 = traj_wave_sum(n_bad), v7 = traj_wave_sum(len);
+    const double v0 = wave_reduce<RedSum>(f_obs), v1 = wave_reduce<RedSum>(seg2), v2 = wave_reduce<RedMin>(mind),
+                 v3 = wave_reduce<RedSum>(n_neg), v4 = wave_reduce<RedSum>(n_act), v5 = wave_reduce<RedSum>(gsq),
+                 v6 = wave_reduce<RedSum>(n_bad), v7 = wave_reduce<RedSum>(len);
     if (lane == 0) {
       sh[wave][0] = v0; sh[wave][1] = v1; sh[wave][2] = v2; sh[wave][3] = v3;
       sh[wave][4] = v4; sh[wave][5] = v5; sh[wave][6] = v6; sh[wave][7] = v7;
     }
   }
   __syncthreads();                        // sh, and every grad_t in nab; cv is free from here
-  const double bad_total = ((sh[0][6] + sh[1][6]) + sh[2][6]) + sh[3][6];
+  const auto sum4 = [&](int v) { return waves_combine<RedSum>(sh[0][v], sh[1][v], sh[2][v], sh[3][v]); };
+  const double bad_total = sum4(6);
 
   double m = 0.0;
   if (state_in == 0) {                    // uniform over the workgroup
@@ -192,10 +179,10 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
       nab[t] = d0; nab[T + t] = d1; nab[2 * T + t] = d2;
       m = fmax(m, traj_norm(d0, d1, d2));
     }
-    m = traj_wave_max(m);
+    m = wave_reduce<RedMax>(m);
     if (lane == 0) shm[wave] = m;
     __syncthreads();
-    m = fmax(fmax(shm[0], shm[1]), fmax(shm[2], shm[3]));
+    m = waves_combine<RedMax>(shm[0], shm[1], shm[2], shm[3]);
   }
 
   int state_out = state_in;
@@ -209,17 +196,17 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
 
   if (tid < TREC) {
     double v = 0.0;
-    if (tid == 2) v = fmin(fmin(sh[0][2], sh[1][2]), fmin(sh[2][2], sh[3][2]));
-    else if (tid == 0) v = ((sh[0][0] + sh[1][0]) + sh[2][0]) + sh[3][0];
-    else if (tid == 1) v = (0.5 * (double)(T - 1)) * (((sh[0][1] + sh[1][1]) + sh[2][1]) + sh[3][1]);
-    else if (tid == 3) v = ((sh[0][3] + sh[1][3]) + sh[2][3]) + sh[3][3];
-    else if (tid == 4) v = ((sh[0][4] + sh[1][4]) + sh[2][4]) + sh[3][4];
-    else if (tid == 5) v = ((sh[0][5] + sh[1][5]) + sh[2][5]) + sh[3][5];
+    if (tid == 2) v = waves_combine<RedMin>(sh[0][2], sh[1][2], sh[2][2], sh[3][2]);
+    else if (tid == 0) v = sum4(0);
+    else if (tid == 1) v = (0.5 * (double)(T - 1)) * sum4(1);
+    else if (tid == 3) v = sum4(3);
+    else if (tid == 4) v = sum4(4);
+    else if (tid == 5) v = sum4(5);
     else if (tid == 6) v = m;
     else if (tid == 7) v = kappa;
     else if (tid == 8) v = bad_total;
     else if (tid == 9) v = (double)state_out;
-    else if (tid == 10) v = ((sh[0][7] + sh[1][7]) + sh[2][7]) + sh[3][7];
+    else if (tid == 10) v = sum4(7);
     records[b * TREC + tid] = v;
   }
   if (tid == 0 && state_out != state_in) state[b] = state_out;

@@ -12,6 +12,7 @@
 // The chunking is a function of n and m alone (tri_splits), so every output repeats bit for bit run to run.
 #include "isdf_common.h"
 #include "launchers.h"
+#include "block_reduce.h"
 
 namespace isdf {
 
@@ -196,18 +197,6 @@ __global__ __launch_bounds__(256) void tri_distance_kernel(const float* __restri
   }
 }
 
-// sum over the 256 threads of a block in a fixed order: lanes by shuffle, then the four waves in wave order (as eval.hip)
-__device__ __forceinline__ double tri_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double tri_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  return v;
-}
-
 __global__ __launch_bounds__(256) void tri_finish_kernel(const float* __restrict__ pts, int64_t n, const float* __restrict__ packed,
                                                          const unsigned long long* __restrict__ keys,
                                                          const double* __restrict__ wpart, int64_t splits, float* __restrict__ dist,
@@ -254,29 +243,14 @@ __global__ __launch_bounds__(256) void tri_finish_kernel(const float* __restrict
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int v = 0; v < TRI_REC; ++v) {
-    const double t = v == 3 ? tri_wave_max(acc[v]) : tri_wave_sum(acc[v]);
+    const double t = v == 3 ? wave_reduce<RedMax>(acc[v]) : wave_reduce<RedSum>(acc[v]);
     if (lane == 0) sh[wave][v] = t;
   }
   __syncthreads();
   if (threadIdx.x < TRI_REC) {
     const int v = threadIdx.x;
-    part[(int64_t)blockIdx.x * TRI_REC + v] = v == 3 ? fmax(fmax(sh[0][v], sh[1][v]), fmax(sh[2][v], sh[3][v]))
-                                                     : ((sh[0][v] + sh[1][v]) + sh[2][v]) + sh[3][v];
-  }
-}
-
-// closing block: the three sums over the per-block partials, each thread a strided share in ascending order, then the block's
-// fixed-order sum; the maximum likewise
-__global__ __launch_bounds__(256) void tri_record_kernel(const double* __restrict__ part, int64_t nPart, double* __restrict__ out) {
-  __shared__ double sh[4];
-  for (int v = 0; v < TRI_REC; ++v) {
-    double t = 0.0;
-    for (int64_t b = threadIdx.x; b < nPart; b += 256) t = v == 3 ? fmax(t, part[b * TRI_REC + v]) : t + part[b * TRI_REC + v];
-    t = v == 3 ? tri_wave_max(t) : tri_wave_sum(t);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) out[v] = v == 3 ? fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3])) : ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    part[(int64_t)blockIdx.x * TRI_REC + v] = v == 3 ? waves_combine<RedMax>(sh[0][v], sh[1][v], sh[2][v], sh[3][v])
+                                                     : waves_combine<RedSum>(sh[0][v], sh[1][v], sh[2][v], sh[3][v]);
   }
 }
 
@@ -321,8 +295,7 @@ int launch_tri_distance(const float* pts, int64_t n, const float* packed, int64_
                        dist, index, closest, winding, part);
     if ((rc = isdf_launch_status())) return rc;
   }
-  hipLaunchKernelGGL(tri_record_kernel, dim3(1), dim3(256), 0, st, part, fin, record);
-  return isdf_launch_status();
+  return launch_reduce_partials(part, fin, TRI_REC, 1u << 3, record, st);      // the three sums, and the maximum of entry 3
 }
 
 }  // namespace isdf

@@ -22,6 +22,7 @@
 // so the bytes do not depend on the split or on arrival order.
 #include "isdf_common.h"
 #include "launchers.h"
+#include "block_reduce.h"
 
 namespace isdf {
 
@@ -92,12 +93,11 @@ __global__ __launch_bounds__(256) void visible_seen_kernel(const int32_t* __rest
   __shared__ int sh[4];
   int c = 0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) c += count[i] > 0 ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  c = wave_reduce<RedSum>(c);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const int t = sh[0] + sh[1] + sh[2] + sh[3];
+    const int t = waves_combine<RedSum>(sh[0], sh[1], sh[2], sh[3]);
     if (t) atomicAdd(n_seen, (unsigned long long)t);
   }
 }

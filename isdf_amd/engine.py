@@ -196,6 +196,17 @@ def to_host(*tensors):
     return out
 
 
+def host_array(x, dtype=None):
+    """a tensor (of any device) or array-like as a numpy array on the host, of `dtype` if one is given"""
+    return np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, dtype=dtype)
+
+
+def _addr(t):
+    """the address of a tensor, NULL for an absent or an empty one: an empty tensor has none to hand over, and the call reads or
+    writes nothing of it then"""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
 class Engine:
     def __init__(self, net: NetConfig, device="cuda"):
         self.lib = _ffi.lib()
@@ -225,12 +236,7 @@ class Engine:
         self._mesher = None       # marching-cubes workspace, count pair and output capacity (isdf_amd.mesh.Mesher)
         self._band = None         # narrow-band workspace and count table (isdf_amd.mesh.BandSelector)
         self._renderer = None     # rendered-view workspace (isdf_amd.render.Renderer)
-        self._eval_ws = None      # partial records of isdf_sdf_metrics
-        self._region_ws = None    # ... and of isdf_region_metrics
-        self._nn_ws = None        # keys and partial sums of isdf_nn_distance
-        self._pose_ws = None      # partial records of isdf_pose_system (callers without a workspace of their own)
-        self._edt_ws = None       # the two int32 volumes of isdf_distance_transform / isdf_occupancy_sdf
-        self._tri_ws = None       # keys, winding partials and partial records of isdf_tri_distance
+        self._scratch_bufs = {}   # call name -> its grow-only uint8 workspace (_scratch)
         self.reduce_buf = None
         self.reduce_extra = 0
         self.reduce_floats = 0
@@ -254,8 +260,7 @@ class Engine:
     def load_params(self, state):
         """state: dict key -> array/tensor (reference state_dict layout)."""
         for k, (off, shp) in self.slices.items():
-            v = torch.as_tensor(np.asarray(state[k].detach().cpu() if torch.is_tensor(state[k]) else state[k]),
-                                dtype=torch.float32).reshape(-1)
+            v = torch.as_tensor(host_array(state[k]), dtype=torch.float32).reshape(-1)
             self.params[off:off + v.numel()].copy_(v)
         self.pack()
 
@@ -680,10 +685,31 @@ class Engine:
         t = t.detach().reshape(-1) if width is None else t.detach().reshape(-1, width)
         return t.to(device=self.device, dtype=dtype).contiguous()
 
-    def _check_volume(self, name, volume):
-        vd = volume.values.device
-        if vd.type != self.device.type or (self.device.index is not None and vd.index != self.device.index):
-            raise ValueError("%s: the ground-truth volume is on %s, the engine on %s" % (name, vd, self.device))
+    def _check_device(self, name, what, t):
+        """`t` lies on this engine's device"""
+        if t.device.type != self.device.type or (self.device.index is not None and t.device.index != self.device.index):
+            raise ValueError("%s: %s is on %s, the engine on %s" % (name, what, t.device, self.device))
+
+    def _scratch(self, name, nbytes):
+        """the uint8 workspace the calls named `name` share: kept across calls, replaced by a larger one when `nbytes` asks for it"""
+        ws = self._scratch_bufs.get(name)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._scratch_bufs[name] = None            # release before growing: the two never need to coexist
+            ws = self._scratch_bufs[name] = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        return ws
+
+    @property
+    def _nn_ws(self):
+        """the workspace isdf_nn_distance last used: it begins with the keys (include/isdf_hip.h), which the tests compare"""
+        return self._scratch_bufs.get("nn_distance")
+
+    def _record_out(self, name, out, rows, width, on=None):
+        """a fresh float64 [rows, width] record tensor, or the caller's `out` checked to be one (and, `on` given, on that device)"""
+        if out is None:
+            return torch.empty(rows, width, dtype=torch.float64, device=self.device)
+        if out.dtype != torch.float64 or out.numel() != rows * width or not out.is_contiguous() or (on is not None and out.device != on):
+            raise ValueError("%s: out must be a contiguous float64 [%d, %d]%s" % (name, rows, width, " on x's device" if on is not None else ""))
+        return out
 
     def sdf_metrics(self, volume, pts, sdf, exclude_zero_gt=True, per_point=False, oob_fill=0.0):
         """(record f64[24], gt [n] or None, valid u8[n] or None) on the device: isdf_sdf_metrics, the ground-truth lookup and
@@ -694,16 +720,14 @@ class Engine:
         n = int(p.shape[0])
         if s.numel() != n:
             raise ValueError("sdf_metrics: %d points but %d sdf values" % (n, s.numel()))
-        self._check_volume("sdf_metrics", volume)
-        if self._eval_ws is None:
-            self._eval_ws = torch.empty(_ffi.SDF_METRICS_WS_BYTES, dtype=torch.uint8, device=self.device)
+        self._check_device("sdf_metrics", "the ground-truth volume", volume.values)
+        ws = self._scratch("sdf_metrics", _ffi.SDF_METRICS_WS_BYTES)
         record = torch.empty(_ffi.METRICS_RECORD, dtype=torch.float64, device=self.device)
         gt = torch.empty(n, dtype=torch.float32, device=self.device) if per_point else None
         valid = torch.empty(n, dtype=torch.uint8, device=self.device) if per_point else None
         _ffi.check(self.lib.isdf_sdf_metrics(C.byref(volume.to_c()), _ffi.ptr(p), _ffi.ptr(s), n, int(bool(exclude_zero_gt)),
                                              float(oob_fill), _ffi.ptr(record), _ffi.ptr(gt), _ffi.ptr(valid),
-                                             _ffi.ptr(self._eval_ws), int(self._eval_ws.numel()), _stream(self.device)),
-                   "isdf_sdf_metrics")
+                                             _ffi.ptr(ws), int(ws.numel()), _stream(self.device)), "isdf_sdf_metrics")
         return record, gt, valid
 
     def region_metrics(self, pts, sdf, volume=None, gt=None, sdf_grad=None, flags=None, delta=0.01, out=None):
@@ -722,7 +746,7 @@ class Engine:
         a = _ffi.RegionArgs()
         keep = [p, s]
         if volume is not None:
-            self._check_volume("region_metrics", volume)
+            self._check_device("region_metrics", "the ground-truth volume", volume.values)
             vc = volume.to_c()
             keep.append(vc)
             a.vol = C.pointer(vc)
@@ -743,14 +767,10 @@ class Engine:
                 setattr(a, name, t.data_ptr() if n else 8)
         a.pts, a.sdf, a.n = p.data_ptr(), s.data_ptr(), n
         a.grad_sets, a.delta = int(sdf_grad is not None), float(delta)
-        if self._region_ws is None:
-            self._region_ws = torch.empty(_ffi.REGION_METRICS_WS_BYTES, dtype=torch.uint8, device=dev)
-        if out is None:
-            out = torch.empty(2, _ffi.REGION_RECORD, dtype=torch.float64, device=dev)
-        elif out.dtype != torch.float64 or out.numel() != 2 * _ffi.REGION_RECORD or not out.is_contiguous():
-            raise ValueError("region_metrics: out must be a contiguous float64 [2, %d]" % _ffi.REGION_RECORD)
-        _ffi.check(self.lib.isdf_region_metrics(C.byref(a), _ffi.ptr(out), _ffi.ptr(self._region_ws),
-                                                int(self._region_ws.numel()), _stream(dev)), "isdf_region_metrics")
+        ws = self._scratch("region_metrics", _ffi.REGION_METRICS_WS_BYTES)
+        out = self._record_out("region_metrics", out, 2, _ffi.REGION_RECORD)
+        _ffi.check(self.lib.isdf_region_metrics(C.byref(a), _ffi.ptr(out), _ffi.ptr(ws), int(ws.numel()), _stream(dev)),
+                   "isdf_region_metrics")
         return out
 
     def nn_distance(self, query, target, want_index=False):
@@ -761,15 +781,12 @@ class Engine:
         n, m = int(q.shape[0]), int(t.shape[0])
         if n > 0 and m < 1:
             raise ValueError("nn_distance: empty target set")
-        need = _ffi.nn_ws_bytes(n)
-        if self._nn_ws is None or self._nn_ws.numel() < need:
-            self._nn_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._scratch("nn_distance", _ffi.nn_ws_bytes(n))
         dist = torch.empty(n, dtype=torch.float32, device=self.device)
         index = torch.empty(n, dtype=torch.int32, device=self.device) if want_index else None
         total = torch.empty(1, dtype=torch.float64, device=self.device)
         _ffi.check(self.lib.isdf_nn_distance(_ffi.ptr(q), n, _ffi.ptr(t), m, _ffi.ptr(dist), _ffi.ptr(index), _ffi.ptr(total),
-                                             _ffi.ptr(self._nn_ws), int(self._nn_ws.numel()), _stream(self.device)),
-                   "isdf_nn_distance")
+                                             _ffi.ptr(ws), int(ws.numel()), _stream(self.device)), "isdf_nn_distance")
         return dist, index, total
 
     def visible_points(self, pts, T_CW, depth, cam, trunc=0.2, want_mask=False):
@@ -788,10 +805,8 @@ class Engine:
         count = torch.empty(n, dtype=torch.int32, device=self.device)
         mask = torch.empty(F, n, dtype=torch.uint8, device=self.device) if want_mask else None
         n_seen = torch.empty(1, dtype=torch.int64, device=self.device)
-        # an empty tensor has no address to hand over, and the call reads or writes none of them then
-        given = lambda t: _ffi.ptr(t) if t is not None and t.numel() else None
-        _ffi.check(self.lib.isdf_visible_points(given(p), n, given(T), given(d), F, H, W, float(cam.fx), float(cam.fy), float(cam.cx),
-                                                float(cam.cy), float(trunc), given(count), given(mask), _ffi.ptr(n_seen),
+        _ffi.check(self.lib.isdf_visible_points(_addr(p), n, _addr(T), _addr(d), F, H, W, float(cam.fx), float(cam.fy), float(cam.cx),
+                                                float(cam.cy), float(trunc), _addr(count), _addr(mask), _ffi.ptr(n_seen),
                                                 _stream(self.device)), "isdf_visible_points")
         return count, mask, n_seen
 
@@ -821,21 +836,14 @@ class Engine:
         a.spacing[:] = [float(v) for v in np.asarray(spacing, np.float64).reshape(3)]
         a.fx, a.fy, a.cx, a.cy = float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy)
         a.trunc, a.max_weight, a.min_depth, a.max_depth = float(trunc), float(max_weight), float(min_depth), float(max_depth)
-        # an empty tensor has no address to hand over, and the call reads none of them then
-        a.depth = d.data_ptr() if d.numel() else None
-        a.T_CW = T.data_ptr() if T.numel() else None
-        a.tsdf = tsdf.data_ptr() if tsdf.numel() else None
-        a.weight = weight.data_ptr() if weight.numel() else None
+        a.depth, a.T_CW, a.tsdf, a.weight = _addr(d), _addr(T), _addr(tsdf), _addr(weight)
         _ffi.check(self.lib.isdf_tsdf_integrate(C.byref(a), _stream(self.device)), "isdf_tsdf_integrate")
         return tsdf, weight
 
     def _edt_workspace(self, dims):
         need = int(self.lib.isdf_edt_ws_bytes(*dims))
         _ffi.check(min(need, 0), "isdf_edt_ws_bytes%s" % (dims,))
-        if self._edt_ws is None or self._edt_ws.numel() < need:
-            self._edt_ws = None                     # release before growing: the two never need to coexist
-            self._edt_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._edt_ws
+        return self._scratch("edt", need)
 
     def _edt_feature(self, name, feature):
         if feature.dim() != 3 or min(feature.shape) < 1:
@@ -886,15 +894,14 @@ class Engine:
         nv, m = int(v.shape[0]), int(f.shape[0])
         T = None
         if transform is not None:
-            A = np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform, np.float32)
+            A = host_array(transform, np.float32)
             if A.shape not in ((3, 4), (4, 4)):
                 raise ValueError("tri_pack: transform must be [3, 4] or [4, 4] (got %s)" % (A.shape,))
             T = (C.c_float * 12)(*[float(x) for x in A[:3].reshape(-1)])
         nbytes = _ffi.tri_packed_bytes(m)
         packed = torch.empty(nbytes // (4 * _ffi.TRI_SLOT_FLOATS), _ffi.TRI_SLOT_FLOATS, dtype=torch.float32, device=self.device)
         counts = torch.empty(2, dtype=torch.int32, device=self.device)
-        given = lambda t: _ffi.ptr(t) if t.numel() else None
-        _ffi.check(self.lib.isdf_tri_pack(given(v), nv, given(f), m, T, given(packed), nbytes, _ffi.ptr(counts),
+        _ffi.check(self.lib.isdf_tri_pack(_addr(v), nv, _addr(f), m, T, _addr(packed), nbytes, _ffi.ptr(counts),
                                           _stream(self.device)), "isdf_tri_pack")
         return packed, counts, m
 
@@ -910,19 +917,16 @@ class Engine:
             raise ValueError("tri_distance: packed must be the contiguous float32 tensor tri_pack returned for %d faces" % m)
         need = int(self.lib.isdf_tri_ws_bytes(n, m))
         _ffi.check(min(need, 0), "isdf_tri_ws_bytes(%d, %d)" % (n, m))
-        if self._tri_ws is None or self._tri_ws.numel() < need:
-            self._tri_ws = None                     # release before growing: the two never need to coexist
-            self._tri_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._scratch("tri_distance", need)
         dev = self.device
         dist = torch.empty(n, dtype=torch.float32, device=dev) if want_dist else None
         index = torch.empty(n, dtype=torch.int32, device=dev) if want_index else None
         closest = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_closest else None
         winding = torch.empty(n, dtype=torch.float32, device=dev) if want_winding else None
         record = torch.empty(_ffi.TRI_RECORD, dtype=torch.float64, device=dev)
-        given = lambda t: _ffi.ptr(t) if t is not None and t.numel() else None
-        _ffi.check(self.lib.isdf_tri_distance(given(p), n, given(packed) if m else None, m, given(dist), given(index),
-                                              given(closest), given(winding), _ffi.ptr(record), _ffi.ptr(self._tri_ws),
-                                              int(self._tri_ws.numel()), _stream(dev)), "isdf_tri_distance")
+        _ffi.check(self.lib.isdf_tri_distance(_addr(p), n, _addr(packed) if m else None, m, _addr(dist), _addr(index),
+                                              _addr(closest), _addr(winding), _ffi.ptr(record), _ffi.ptr(ws), int(ws.numel()),
+                                              _stream(dev)), "isdf_tri_distance")
         return dist, index, closest, winding, record
 
     # ---- frame-to-map pose alignment ---------------------------------------------------
@@ -933,7 +937,7 @@ class Engine:
             raise ValueError("%s: depth must be [F, H, W] (got %s)" % (name, tuple(depth.shape)))
         F, H, W = (int(v) for v in depth.shape)
         d = self._flat(depth, torch.float32)
-        T = np.asarray(T_WC.detach().cpu() if torch.is_tensor(T_WC) else T_WC)
+        T = host_array(T_WC)
         if T.shape[-2:] == (4, 4):
             T = T.reshape(-1, 4, 4)[:, :3, :]
         elif T.ndim == 0 or T.shape[-1] != 12:
@@ -942,8 +946,7 @@ class Engine:
         B = int(T.shape[0])
         fop = None
         if frame_of_pose is not None:
-            fop = np.ascontiguousarray(np.asarray(frame_of_pose.detach().cpu() if torch.is_tensor(frame_of_pose) else frame_of_pose)
-                                       .reshape(-1), dtype=np.int32)
+            fop = np.ascontiguousarray(host_array(frame_of_pose).reshape(-1), dtype=np.int32)
             if fop.size != B:
                 raise ValueError("%s: %d poses but %d frame indices" % (name, B, fop.size))
         stride = int(stride)
@@ -951,7 +954,7 @@ class Engine:
         a.B, a.F, a.H, a.W, a.stride = B, F, H, W, stride
         a.fx, a.fy, a.cx, a.cy = float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy)
         a.min_depth, a.max_depth = float(min_depth), float(max_depth)
-        a.depth = d.data_ptr() if d.numel() else None
+        a.depth = _addr(d)
         a.T_WC = T.ctypes.data if B else None
         a.frame_of_pose = None if fop is None else fop.ctypes.data
         n_pix = (-(-H // stride)) * (-(-W // stride)) if stride >= 1 else 0
@@ -965,8 +968,7 @@ class Engine:
         above max_depth gets the camera centre.  cam: anything with fx, fy, cx, cy.  No host synchronisation."""
         a, keep, B, n_pix = self._pose_args("pose_points", depth, T_WC, cam, frame_of_pose, stride, min_depth, max_depth)
         pts = torch.empty(B * n_pix, 3, dtype=torch.float32, device=self.device)
-        _ffi.check(self.lib.isdf_pose_points(C.byref(a), _ffi.ptr(pts) if pts.numel() else None, _stream(self.device)),
-                   "isdf_pose_points")
+        _ffi.check(self.lib.isdf_pose_points(C.byref(a), _addr(pts), _stream(self.device)), "isdf_pose_points")
         return pts
 
     def pose_system(self, depth, T_WC, cam, pts, sdf, grad, frame_of_pose=None, stride=4, min_depth=0.0, max_depth=float("inf"),
@@ -986,13 +988,8 @@ class Engine:
         need = int(self.lib.isdf_pose_ws_bytes(B))
         _ffi.check(min(need, 0), "isdf_pose_ws_bytes(%d)" % B)
         if workspace is None:
-            if self._pose_ws is None or self._pose_ws.numel() < need:
-                self._pose_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            workspace = self._pose_ws
-        if out is None:
-            out = torch.empty(B, _ffi.POSE_RECORD, dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or out.numel() != B * _ffi.POSE_RECORD or not out.is_contiguous():
-            raise ValueError("pose_system: out must be a contiguous float64 [%d, %d]" % (B, _ffi.POSE_RECORD))
+            workspace = self._scratch("pose_system", need)
+        out = self._record_out("pose_system", out, B, _ffi.POSE_RECORD)
         _ffi.check(self.lib.isdf_pose_system(C.byref(a), _ffi.ptr(p), _ffi.ptr(s), _ffi.ptr(g), float(huber), float(trunc),
                                              _ffi.ptr(out), _ffi.ptr(workspace), int(workspace.numel()), _stream(self.device)),
                    "isdf_pose_system")
@@ -1004,20 +1001,19 @@ class Engine:
         offsets [S,3] and radii [S] (or a scalar) as HOST arrays, checked by the call and handed on as launch arguments"""
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[-1] != 3 or x.dtype != torch.float32 or not x.is_contiguous():
             raise ValueError("%s: x must be a contiguous float32 tensor [B, T, 3]" % name)
-        if x.device.type != self.device.type or (self.device.index is not None and x.device.index != self.device.index):
-            raise ValueError("%s: x is on %s, the engine on %s" % (name, x.device, self.device))
-        off = np.ascontiguousarray(np.asarray(offsets.detach().cpu() if torch.is_tensor(offsets) else offsets, dtype=np.float32))
+        self._check_device(name, "x", x)
+        off = np.ascontiguousarray(host_array(offsets, np.float32))
         if off.ndim != 2 or off.shape[1] != 3:
             raise ValueError("%s: offsets must be [S, 3] (got %s)" % (name, off.shape))
         S = int(off.shape[0])
-        rad = np.asarray(radii.detach().cpu() if torch.is_tensor(radii) else radii, dtype=np.float32)
+        rad = host_array(radii, np.float32)
         rad = np.ascontiguousarray(np.broadcast_to(rad.reshape(-1), (S,)) if rad.size == 1 else rad.reshape(-1))
         if rad.size != S:
             raise ValueError("%s: %d offsets but %d radii" % (name, S, rad.size))
         B, T = int(x.shape[0]), int(x.shape[1])
         a = _ffi.TrajArgs()
         a.B, a.T, a.S = B, T, S
-        a.x = x.data_ptr() if x.numel() else None
+        a.x = _addr(x)
         a.offsets = off.ctypes.data if S else None
         a.radii = rad.ctypes.data if S else None
         return a, (off, rad), B, T, S
@@ -1028,8 +1024,7 @@ class Engine:
         offsets [S,3], radii [S] or a scalar: host or device, read on the host.  No host synchronisation."""
         a, keep, B, T, S = self._traj_args("traj_points", x, offsets, radii)
         q = torch.empty(B * T * S, 3, dtype=torch.float32, device=self.device)
-        _ffi.check(self.lib.isdf_traj_points(C.byref(a), _ffi.ptr(q) if q.numel() else None, _stream(self.device)),
-                   "isdf_traj_points")
+        _ffi.check(self.lib.isdf_traj_points(C.byref(a), _addr(q), _stream(self.device)), "isdf_traj_points")
         return q
 
     def traj_step(self, x, state, offsets, radii, sdf, grad, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=8.0, max_step=0.05, tol=1e-5,
@@ -1052,17 +1047,14 @@ class Engine:
         n = B * T * S
         if not (s.numel() == int(g.shape[0]) == n):
             raise ValueError("traj_step: %d x %d x %d needs %d sdf values and gradients (got %d, %d)" % (B, T, S, n, s.numel(), g.shape[0]))
-        if out is None:
-            out = torch.empty(B, _ffi.TRAJ_RECORD, dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or out.numel() != B * _ffi.TRAJ_RECORD or not out.is_contiguous() or out.device != x.device:
-            raise ValueError("traj_step: out must be a contiguous float64 [%d, %d] on x's device" % (B, _ffi.TRAJ_RECORD))
+        out = self._record_out("traj_step", out, B, _ffi.TRAJ_RECORD, on=x.device)
         if q_out is not None and (q_out.dtype != torch.float32 or q_out.numel() != n * 3 or not q_out.is_contiguous()
                                   or q_out.device != x.device):
             raise ValueError("traj_step: q_out must be a contiguous float32 tensor of %d x 3 values on x's device" % n)
         gout = torch.empty(B, T, 3, dtype=torch.float64, device=self.device) if want_grad else None
-        a.state = state.data_ptr() if B else None
+        a.state = _addr(state)
         a.eps, a.w_obs, a.w_smooth, a.eta, a.max_step, a.tol = (float(v) for v in (eps, w_obs, w_smooth, eta, max_step, tol))
-        _ffi.check(self.lib.isdf_traj_step(C.byref(a), _ffi.ptr(s) if n else None, _ffi.ptr(g) if n else None, _ffi.ptr(out),
+        _ffi.check(self.lib.isdf_traj_step(C.byref(a), _addr(s), _addr(g), _ffi.ptr(out),
                                            _ffi.ptr(q_out), _ffi.ptr(gout), _stream(self.device)), "isdf_traj_step")
         return (out, gout) if want_grad else out
 
@@ -1083,7 +1075,7 @@ class Engine:
         if volume is not None:
             if p is None:
                 raise ValueError("slice_images: the ground truth needs the points")
-            self._check_volume("slice_images", volume)
+            self._check_device("slice_images", "the ground-truth volume", volume.values)
         cost = chomp_eps is not None
 
         def out(want, *shape, dtype=torch.float32):
@@ -1111,8 +1103,7 @@ class Engine:
         H, W = int(H), int(W)
         if H < 0 or W < 0:
             raise ValueError("plane_points: H and W must be >= 0 (got %d, %d)" % (H, W))
-        vec = [(C.c_float * 3)(*[float(x) for x in np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, np.float64).reshape(3)])
-               for v in (origin, du, dv)]
+        vec = [(C.c_float * 3)(*[float(x) for x in host_array(v, np.float64).reshape(3)]) for v in (origin, du, dv)]
         pts = torch.empty(H, W, 3, dtype=torch.float32, device=self.device)
         _ffi.check(self.lib.isdf_plane_points(vec[0], vec[1], vec[2], H, W, _ffi.ptr(pts), _stream(self.device)),
                    "isdf_plane_points")

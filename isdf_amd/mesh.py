@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .engine import _stream, to_host
+from .engine import _stream, host_array, to_host
 
 
 def grid_index_to_world(dim, scene_scale, bounds_transform):
@@ -74,8 +74,7 @@ class Mesher:
         args = _ffi.McArgs()
         args.volume, args.D0, args.D1, args.D2, args.level = vol.data_ptr(), D0, D1, D2, float(level)
         if index_to_world is not None:
-            A = np.asarray(index_to_world.detach().cpu() if torch.is_tensor(index_to_world) else index_to_world,
-                           np.float32).reshape(3, 4)
+            A = host_array(index_to_world, np.float32).reshape(3, 4)
             args.has_transform = 1
             args.index_to_world[:] = [float(x) for x in A.reshape(-1)]
         nb = self.lib.isdf_mesh_ws_bytes(D0, D1, D2)
@@ -126,7 +125,7 @@ MAX_WIDEN = 6            # band attempts of extract_surface(widen=True) before t
 
 
 def _affine_rows(index_to_world):
-    A = np.asarray(index_to_world.detach().cpu() if torch.is_tensor(index_to_world) else index_to_world, np.float32)
+    A = host_array(index_to_world, np.float32)
     return (C.c_float * 12)(*[float(x) for x in A.reshape(3, 4).reshape(-1)])
 
 

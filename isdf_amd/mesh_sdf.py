@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import metrics
+from .engine import host_array
 
 CHUNK = 1 << 20      # query points per call of mesh_volume
 
@@ -50,7 +51,7 @@ class PackedMesh:
         # what sample_surface reads: the transformed vertices (torch's rounding, not the kernel's chain: sampling only)
         v = v.to(torch.float32)
         if transform is not None:
-            A = torch.as_tensor(np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform, np.float32)[:3],
+            A = torch.as_tensor(host_array(transform, np.float32)[:3],
                                 device=self.device)
             v = v @ A[:, :3].T + A[:, 3]
         self.vertices, self.faces = v, f.to(torch.int64)

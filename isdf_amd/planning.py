@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from .engine import host_array
 
 REC = _ffi.TRAJ_RECORD
 MOVING, CONVERGED, INVALID = 0, 1, 2
@@ -103,8 +104,8 @@ def _setup(obj, x, offsets, radii, field):
         raise ValueError("trajectories must be [B, T, 3] or [T, 3] (got %s)" % (tuple(x.shape),))
     x = x.detach().to(device=eng.device, dtype=torch.float32).contiguous().clone()
     off = np.zeros((1, 3), np.float32) if offsets is None else np.ascontiguousarray(
-        np.asarray(offsets.detach().cpu() if torch.is_tensor(offsets) else offsets, dtype=np.float32)).reshape(-1, 3)
-    rad = np.asarray(radii.detach().cpu() if torch.is_tensor(radii) else radii, dtype=np.float32).reshape(-1)
+        host_array(offsets, np.float32)).reshape(-1, 3)
+    rad = host_array(radii, np.float32).reshape(-1)
     rad = np.ascontiguousarray(np.broadcast_to(rad, (off.shape[0],)) if rad.size == 1 else rad)
     if rad.size != off.shape[0]:
         raise ValueError("%d offsets but %d radii" % (off.shape[0], rad.size))

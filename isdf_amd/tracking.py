@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from .engine import host_array
 
 REC = _ffi.POSE_RECORD
 _TRIU = np.triu_indices(6)
@@ -104,7 +105,7 @@ def _setup(obj, depth, T_WC, frame_of_pose, field):
     T = np.array(T_WC.detach().cpu() if torch.is_tensor(T_WC) else T_WC, dtype=np.float64).reshape(-1, 4, 4)
     fop = None
     if frame_of_pose is not None:
-        fop = np.asarray(frame_of_pose.detach().cpu() if torch.is_tensor(frame_of_pose) else frame_of_pose, np.int32).reshape(-1)
+        fop = host_array(frame_of_pose, np.int32).reshape(-1)
         if fop.size != T.shape[0]:
             raise ValueError("%d poses but %d frame indices" % (T.shape[0], fop.size))
     if field is None:

@@ -64,6 +64,32 @@ def points32(depth, T_WC, cam, frame_of_pose=None, stride=4, min_depth=0.0, max_
     return np.concatenate(out), np.concatenate(ok)
 
 
+def _pose_terms(pts, sdf, grad, valid, T, b, n, hub, tr):
+    """(terms [used points, 32], used [n] bool, ok [n] bool) of pose b: every product in the kernel's order"""
+    s = slice(b * n, (b + 1) * n)
+    r = np.asarray(sdf[s], np.float32).astype(np.float64)
+    a = np.abs(r)
+    ok = np.asarray(valid[s], bool)
+    with np.errstate(invalid="ignore"):
+        used = ok & (a <= tr)
+    r, a = r[used], a[used]
+    g = np.asarray(grad[s], np.float32).astype(np.float64)[used]
+    d = np.asarray(pts[s], np.float32).astype(np.float64)[used] - T[b, [3, 7, 11]]
+    quad = a <= hub
+    w = np.where(quad, 1.0, hub / np.where(quad, 1.0, a))
+    J = np.concatenate([g, np.stack([d[:, 1] * g[:, 2] - d[:, 2] * g[:, 1], d[:, 2] * g[:, 0] - d[:, 0] * g[:, 2],
+                                     d[:, 0] * g[:, 1] - d[:, 1] * g[:, 0]], -1)], -1)
+    wr = w * r
+    terms = np.zeros((len(r), REC))
+    terms[:, 0] = 1.0
+    terms[:, 2] = wr * r
+    terms[:, 3] = np.where(quad, 0.5 * (r * r), hub * (a - 0.5 * hub))
+    terms[:, 4:10] = wr[:, None] * J
+    terms[:, 10:31] = (w[:, None] * J)[:, TRIU[0]] * J[:, TRIU[1]]
+    terms[:, 31] = a
+    return terms, used, ok
+
+
 def records64(pts, sdf, grad, valid, T_WC, huber=0.05, trunc=0.3):
     """(records [B, 32], scale [B, 32]) in float64 from the float32 arrays: the header's record, and per entry the sum of |term|
     (the counts' scale is the count).  huber and trunc are rounded to float32 first, as the ABI takes them."""
@@ -73,30 +99,24 @@ def records64(pts, sdf, grad, valid, T_WC, huber=0.05, trunc=0.3):
     hub, tr = float(np.float32(huber)), float(np.float32(trunc))
     rec, scale = np.zeros((B, REC)), np.zeros((B, REC))
     for b in range(B):
-        s = slice(b * n, (b + 1) * n)
-        r = np.asarray(sdf[s], np.float32).astype(np.float64)
-        a = np.abs(r)
-        ok = np.asarray(valid[s], bool)
-        with np.errstate(invalid="ignore"):
-            used = ok & (a <= tr)
-        r, a = r[used], a[used]
-        g = np.asarray(grad[s], np.float32).astype(np.float64)[used]
-        d = np.asarray(pts[s], np.float32).astype(np.float64)[used] - T[b, [3, 7, 11]]
-        quad = a <= hub
-        w = np.where(quad, 1.0, hub / np.where(quad, 1.0, a))
-        J = np.concatenate([g, np.stack([d[:, 1] * g[:, 2] - d[:, 2] * g[:, 1], d[:, 2] * g[:, 0] - d[:, 0] * g[:, 2],
-                                         d[:, 0] * g[:, 1] - d[:, 1] * g[:, 0]], -1)], -1)
-        wr = w * r
-        terms = np.zeros((len(r), REC))
-        terms[:, 0] = 1.0
-        terms[:, 2] = wr * r
-        terms[:, 3] = np.where(quad, 0.5 * (r * r), hub * (a - 0.5 * hub))
-        terms[:, 4:10] = wr[:, None] * J
-        terms[:, 10:31] = (w[:, None] * J)[:, TRIU[0]] * J[:, TRIU[1]]
-        terms[:, 31] = a
+        terms, _, ok = _pose_terms(pts, sdf, grad, valid, T, b, n, hub, tr)
         rec[b], scale[b] = terms.sum(0), np.abs(terms).sum(0)
         rec[b, 1] = scale[b, 1] = ok.sum()
     return rec, scale
+
+
+def terms64(pts, sdf, grad, valid, T_WC, huber=0.05, trunc=0.3):
+    """[B, n_pix, 32]: what every lattice pixel adds to its pose's record (zero where it is not used; column 1 counts the valid
+    pixels), for the exact-order model of tests/reduce_model.py"""
+    T = _poses12(T_WC).astype(np.float64)
+    B = T.shape[0]
+    n = len(sdf) // B
+    out = np.zeros((B, n, REC))
+    for b in range(B):
+        terms, used, ok = _pose_terms(pts, sdf, grad, valid, T, b, n, float(np.float32(huber)), float(np.float32(trunc)))
+        out[b, used] = terms
+        out[b, :, 1] = ok
+    return out
 
 
 # ---- analytic fields: float64 value, central-difference gradient (h = 1e-4), both rounded to float32 ---------------------

@@ -19,6 +19,7 @@ import torch
 
 from tests import eval_fixed_model as fm
 from tests import eval_model as em
+from tests import reduce_model as rm
 
 pytestmark = pytest.mark.gpu
 
@@ -155,6 +156,39 @@ def test_sizes_around_the_block_and_grid_limits(eng, g, n):
     nograd, model = _run(eng, g, pts, sdf, flags=flags)                      # gradient bits without sdf_grad are not honoured
     _sums_close(nograd, model)
     assert nograd[:, 24:].max() == 0
+
+
+def _region_terms(sdf, gt, flags):
+    """[n, 2, 15] float64: what every point adds to entries 0..14 of the two sets on the given-ground-truth leg"""
+    s, g = sdf.astype(np.float64), np.asarray(gt, np.float64)
+    d = np.abs(s - g)
+    c = np.zeros((len(s), 15))
+    c[:, 0], c[:, 1], c[:, 2] = 1.0, 1.0, d
+    for b in range(6):
+        m = (g > em.BIN_LIMITS[b]) & (g < em.BIN_LIMITS[b + 1])
+        c[:, 3 + b], c[:, 9 + b] = np.where(m, d, 0.0), m
+    return np.stack([np.where((flags >> k & 1).astype(bool)[:, None], c, 0.0) for k in range(2)], 1)
+
+
+@pytest.mark.parametrize("n", [257, 4099])
+def test_region_records_equal_the_ordered_sums_bit_for_bit(eng, n):
+    """entries 0..14 of both sets against tests/reduce_model.py on the float64 ground-truth leg; points in one set, in both and
+    in neither; magnitudes from 2^-20 to 2^20, so another order gives other bytes (asserted against np.sum)"""
+    from isdf_amd import _ffi
+    rng = np.random.RandomState(n)
+    sdf = rm.wide(rng, n)
+    gt = rm.wide(rng, n).astype(np.float64) * (1.0 + rng.uniform(0, 2.0 ** -30, n))      # doubles no float32 holds
+    flags = rng.randint(0, 4, n).astype(np.uint8)
+    assert all((flags == f).sum() > n // 8 for f in range(4))
+    pts = rng.uniform(-1, 1, (n, 3)).astype(np.float32)
+    rec = eng.region_metrics(_cuda(pts), _cuda(sdf), gt=_cuda(gt), flags=_cuda(flags)).cpu().numpy()
+    terms = _region_terms(sdf, gt, flags)
+    assert _ffi.REGION_METRICS_WS_BYTES == 1024 * 2 * _ffi.REGION_RECORD * 8            # ISDF_METRICS_MAX_BLOCKS partial records
+    model = rm.close_strided(rm.grid_stride_record(terms.reshape(n, 30), 1024)).reshape(2, 15)
+    plain = terms.sum(0)
+    print("n = %d: entries where the ordered sum is not np.sum: %d of 30" % (n, (model != plain).sum()))
+    assert (model != plain).any(1).all()
+    assert rec[:, :15].tobytes() == model.tobytes(), np.argwhere(rec[:, :15] != model)
 
 
 def test_all_outside_points(eng, g):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import eval_model as em
+from tests import reduce_model as rm
 
 pytestmark = pytest.mark.gpu
 
@@ -106,6 +107,72 @@ def test_record_is_bit_identical_run_to_run_and_stable_under_permutation(eng, g)
     a = a.cpu().numpy()
     assert np.array_equal(a[[0, 1]], c[[0, 1]]) and np.array_equal(a[9:15], c[9:15])
     assert np.abs(a - c).max() <= _bound(g["pts"], g["zeroed/gt"])
+
+
+def _chomp_as_the_kernel(s, e):
+    """eval.hip's chomp(): the three assignments, the quadratic written (1.0 / (2.0 * e)) * (s - e) * (s - e)"""
+    c = -s + 0.5 * e
+    c = np.where(s > 0.0, (1.0 / (2.0 * e)) * (s - e) * (s - e), c)
+    return np.where(s > e, 0.0, c)
+
+
+def _sdf_metrics_terms(sdf, gt, valid):
+    """[n, 24] float64: what every point adds to the record, from the float32 inputs and the device's own per-point ground
+    truth and validity (out of bounds = the NaN the call was given as oob_fill)"""
+    s, g = sdf.astype(np.float64), gt.astype(np.float64)
+    d = np.abs(s - g)
+    t = np.zeros((len(s), em.RECORD))
+    t[:, 0], t[:, 1], t[:, 2] = 1.0, 1.0, d
+    lim = em.BIN_LIMITS.astype(np.float32)                      # compared in float32 against the float32 ground truth
+    for b in range(6):
+        with np.errstate(invalid="ignore"):
+            m = (gt > lim[b]) & (gt < lim[b + 1])
+        t[:, 3 + b], t[:, 9 + b] = np.where(m, d, 0.0), m
+    for e, eps in enumerate(em.EPSILONS):
+        cp, cg = _chomp_as_the_kernel(s, eps), _chomp_as_the_kernel(g, eps)
+        t[:, 15 + 3 * e], t[:, 16 + 3 * e], t[:, 17 + 3 * e] = np.abs(cp - cg), cp, cg
+    t[~valid] = 0.0
+    t[:, 1] = ~np.isnan(gt)
+    return t
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 4099, 1024 * 256 + 257])
+def test_sdf_metrics_record_equals_the_ordered_sums_bit_for_bit(eng, n):
+    """all 24 entries against tests/reduce_model.py: a grid-stride share per thread, the block's order, the strided closing.
+    Volume and predictions span 2^-20 .. 2^20 in magnitude, so another order gives other bytes (asserted against np.sum; a
+    single term has one order only).  The last size is past 1024 blocks of 256: threads take a second element."""
+    from isdf_amd.metrics import GtVolume
+    rng = np.random.RandomState(n % 1000)
+    vol = GtVolume(rm.wide(rng, (9, 8, 7)), [0.5, 0.25, 0.5], [-2.0, -1.0, -1.5], "cuda")
+    pts = rng.uniform([-2.2, -1.1, -1.6], [2.2, 0.85, 1.6], (n, 3)).astype(np.float32)     # about one in four outside
+    sdf = rm.wide(rng, n)
+    sdf[::5] = np.abs(sdf[::5])                                  # every branch of the CHOMP cost
+    vol.values.view(-1)[::11] = 0.0                              # ground truth == 0 on some faces: in bounds, not valid
+    pts[::13] = np.float32([-2.0, -1.0, -1.5]) + np.float32([0.5, 0.25, 0.5]) * rng.randint(0, 7, (len(pts[::13]), 3)).astype(np.float32)
+    rec, gt, valid = eng.sdf_metrics(vol, _cuda(pts), _cuda(sdf), per_point=True, oob_fill=float("nan"))
+    rec, gt, valid = rec.cpu().numpy(), gt.cpu().numpy(), valid.cpu().numpy().astype(bool)
+    terms = _sdf_metrics_terms(sdf, gt, valid)
+    model = rm.close_strided(rm.grid_stride_record(terms, 1024))
+    plain = terms.sum(0)
+    print("n = %d: %d in bounds, %d valid; columns where the ordered sum is not np.sum: %d" % (n, rec[1], rec[0], (model != plain).sum()))
+    if n >= 255:
+        assert 0 < rec[0] < rec[1] < n and (model != plain).any()
+    assert rec.tobytes() == model.tobytes(), np.flatnonzero(rec != model)
+
+
+@pytest.mark.parametrize("n", [1, 257, 65536 + 300])
+def test_nn_dist_sum_equals_the_ordered_sum_of_the_returned_distances(eng, n):
+    """distances from 2^-20 to 2^20 against three targets; the last size gives more than 256 partials, so the closing threads take
+    a second one"""
+    rng = np.random.RandomState(2)             # a seed at which both larger sizes' ordered sums differ from np.sum
+    t = rng.uniform(-1e-7, 1e-7, (3, 3)).astype(np.float32)
+    q = (rm.wide(rng, (n, 1)) * rng.standard_normal((n, 3))).astype(np.float32)
+    dist, _, total = eng.nn_distance(_cuda(q), _cuda(t))
+    dist = dist.cpu().numpy()
+    model = rm.ordered_sum(dist)
+    if n > 1:
+        assert model != dist.astype(np.float64).sum() and dist.max() > 2.0 ** 20 * dist.min()
+    assert np.float64(total.item()).tobytes() == np.float64(model).tobytes()
 
 
 def _keys(eng, n):

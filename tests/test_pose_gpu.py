@@ -11,6 +11,7 @@ import torch
 
 from isdf_amd import tracking
 from tests import pose_model as pm
+from tests import reduce_model as rm
 
 pytestmark = pytest.mark.gpu
 
@@ -114,6 +115,36 @@ def test_records_are_within_the_reordering_bound_of_the_float64_model(eng, cases
     assert (rec[:, 0] >= 64).all() and (rec[:, 1] == c["model_valid"].reshape(len(c["T"]), -1).sum(1)).all()
     if name == "120x160 stride 1":
         assert c["model_valid"].size // 2 == 19200 > 64 * 256              # more than one pass of the capped grid
+
+
+@pytest.mark.parametrize("name", ["12x16 stride 1", "120x160 stride 1"])
+def test_records_equal_the_ordered_sums_of_the_model_bit_for_bit(eng, cases, name):
+    """all 32 entries against tests/reduce_model.py: a grid-stride share per thread, the block's order, then a pose's partial
+    records in block order.  192 pixels are one partial block; 19 200 are more than 64 x 256, so threads take a second pixel.
+    Residuals and gradients span 2^-20 .. 2^20 in magnitude, so another order gives other bytes (asserted against np.sum)."""
+    if name == "12x16 stride 1":
+        cam, T = pm.cam_of(12, 16, 15.0), pm.poses8()[:2]
+        c = dict(depth=pm.render(T, cam, seed=6, invalid_frac=0.1), T=pm.perturb(T, 0.03, 2.0, seed=7), cam=cam,
+                 kw=dict(frame_of_pose=None, stride=1, min_depth=0.0, max_depth=float("inf")))
+        c["model_valid"] = pm.points32(c["depth"], c["T"], cam, **c["kw"])[1]
+    else:
+        c = cases[name]
+    n = c["model_valid"].size
+    rng = np.random.RandomState(n)
+    sdf, grad = rm.wide(rng, n), rm.wide(rng, (n, 3))
+    sdf[::17] = np.float32(2.0 ** 21)                   # beyond the truncation: not used
+    sdf[5::29] = np.nan
+    huber, trunc = 1.0, 2.0 ** 20                       # about half of the residuals on either branch of the Huber weight
+    rec, (pts, _, _) = _system(eng, c, sdf=_cuda(sdf), grad=_cuda(grad), huber=huber, trunc=trunc)
+    terms = pm.terms64(pts, sdf, grad, c["model_valid"], c["T"], huber, trunc)
+    assert terms.shape == (2, n // 2, 32)
+    model = np.stack([rm.close_serial(rm.grid_stride_record(t, 64)) for t in terms])       # ISDF_POSE_MAX_BLOCKS
+    plain = terms.sum(1)
+    print("%s: used %s of valid %s; entries where the ordered sum is not np.sum: %s of 32"
+          % (name, rec[:, 0].astype(int).tolist(), rec[:, 1].astype(int).tolist(), (model != plain).sum(1).tolist()))
+    assert (0 < rec[:, 0]).all() and (rec[:, 0] < rec[:, 1]).all() and (rec[:, 1] < n // 2).all()
+    assert (model != plain).any(1).all()
+    assert rec.tobytes() == model.tobytes(), np.argwhere(rec != model)
 
 
 def test_huber_and_truncation_borders(eng):

@@ -4,9 +4,11 @@
                           float32 operation is rounded once, as the kernel's are: the file is built without contraction)
     distance64 / winding64   float64 models of the distance (the same regions, plain double arithmetic) and of the generalised
                           winding number
-    record                the ordered sums of the record (the kernel's fixed summation order, in double)
+    record                the ordered sums of the record (the kernels' one summation order, tests/reduce_model.py)
 """
 import numpy as np
+
+from tests.reduce_model import ordered_sum
 
 F = np.float32
 TILE, SLOT = 256, 24
@@ -149,32 +151,10 @@ def winding64(vertices, faces, pts, block=512):
     return out
 
 
-def _block_sum(x):
-    """the kernels' fixed order over one block of 256 values: lanes by shuffle halving, then the four waves in wave order"""
-    x = np.asarray(x, np.float64).reshape(4, 64).copy()
-    o = 32
-    while o:
-        x[:, :o] = x[:, :o] + x[:, o:2 * o]
-        o >>= 1
-    return ((x[0, 0] + x[1, 0]) + x[2, 0]) + x[3, 0]
-
-
-def _ordered_sum(values):
-    """per-block sums of 256, then one closing block: each thread a strided share in ascending order, then the block's sum"""
-    x = np.asarray(values, np.float64)
-    nb = (len(x) + 255) // 256
-    x = np.concatenate([x, np.zeros(nb * 256 - len(x))])
-    part = np.array([_block_sum(x[b * 256:(b + 1) * 256]) for b in range(nb)])
-    t = np.zeros(256)
-    for b in range(nb):
-        t[b % 256] += part[b]
-    return _block_sum(t)
-
-
 def record(dist):
     """the four doubles of the record for the per-point distances `dist` (NaN = a non-finite query point)"""
     d = np.asarray(dist, np.float64)
     fin = ~np.isnan(d)
     with np.errstate(invalid="ignore"):
-        return np.array([_ordered_sum(np.where(fin, d, 0.0)), float(fin.sum()), float((~fin).sum()),
+        return np.array([ordered_sum(np.where(fin, d, 0.0)), float(fin.sum()), float((~fin).sum()),
                          d[fin].max() if fin.any() else 0.0])
