@@ -972,6 +972,58 @@ int64_t isdf_tri_ws_bytes(int64_t n, int64_t m);
 int isdf_tri_distance(const float* pts, int64_t n, const float* packed, int64_t m, float* dist, int32_t* index, float* closest,
                       float* winding, double* record, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- routing through the map: geodesic distance field of a free-space mask and the path down it --------------------------
+ * The global half of planning (the local half is isdf_traj_step, which deforms a seed and cannot change which side of an obstacle
+ * it passes): shortest routes over the free voxels of a grid.  The reference has no counterpart.  Volumes are [nx][ny][nz],
+ * row-major, k fastest; `free` is u8 (non-zero = free), distances are int32; at most ISDF_ROUTE_MAX_VOXELS voxels.
+ *
+ * The graph.  Voxels are 26-connected with the integer chamfer weights <3, 4, 5>: w(p, q) = 3 for a face neighbour (one
+ * coordinate differs), 4 for an edge neighbour (two), 5 for a corner neighbour (three).  A move p -> q exists iff both voxels are
+ * inside the grid and free; there is no separate corner-cutting rule (the safety margin belongs to the mask).  dist[p] is the
+ * cost of the cheapest path from p to any goal, ISDF_ROUTE_NONE where p is blocked or no goal can be reached.  A simple path
+ * costs at most 5 * ISDF_ROUTE_MAX_VOXELS < ISDF_ROUTE_NONE: nothing saturates.
+ *
+ * isdf_route_init: dist <- ISDF_ROUTE_NONE everywhere, then dist <- 0 at every goal (device int32 [n_goals][3], voxel coordinates
+ * i, j, k) that is inside the grid and free; other goals are ignored.  n_goals = 0 is allowed (goals may then be NULL).  Two
+ * launches at most.
+ *
+ * isdf_route_relax: `rounds` rounds of two launches each, dist -> workspace -> dist, every launch
+ *   out[p] = min(in[p], min over the 26 neighbours q inside the grid of in[q] + w(p, q))     for free p;  blocked p keep NONE
+ * applied tile by tile: a workgroup loads ISDF_ROUTE_TILE^3 voxels and their one-voxel halo, repeats the update inside the tile
+ * until it stops changing (or a cap is reached) and writes the tile back.  Values only decrease and each is the cost of a real
+ * path, so the fixed point is the exact shortest-path distance whatever the tile, cap or number of launches: once a round changes
+ * nothing, dist is that fixed point, bit for bit.  changed: device int32 [rounds], zeroed by the call (an asynchronous memset);
+ * changed[r] = 1 iff round r lowered any voxel.  No host synchronisation: the caller decides when to look.  dist must come from
+ * isdf_route_init (or an earlier relax) on the same mask.
+ *
+ * isdf_route_trace: B paths, one per start (device int32 [B][3]).  From p = start, step to the FIRST neighbour q, in the order
+ *   (di, dj, dk) lexicographic over -1..1 without (0, 0, 0):  (-1,-1,-1), (-1,-1,0), (-1,-1,1), (-1,0,-1), ... , (1,1,1),
+ * that lies inside the grid and has dist[q] + w(p, q) == dist[p]; stop at dist == 0.  On a converged field one always exists.
+ * path: device int32 [B][max_len], the linear voxel indices (i * ny + j) * nz + k from the start to the goal; len: device int32
+ * [B], the number of voxels including both ends; 0 for a start that is outside the grid, blocked or unreachable; -1 if max_len
+ * is too small or no neighbour matches (a field that was not converged) -- the voxels found so far stay in path, and nothing is
+ * written past max_len.  A path of cost c has at most c / 3 + 1 voxels.  One launch, one wave per path.
+ *
+ * ISDF_EINVAL, before anything is launched: a NULL free / dist / changed / starts / path / len (goals when n_goals > 0), a side
+ * < 1, more than ISDF_ROUTE_MAX_VOXELS voxels, rounds < 1, n_goals or B < 0, max_len < 1.  ISDF_EWORKSPACE: a workspace that is
+ * NULL or smaller than isdf_route_ws_bytes. */
+#define ISDF_ROUTE_NONE 1073741824          /* 2^30 */
+#define ISDF_ROUTE_MAX_VOXELS 134217728     /* 2^27 */
+#define ISDF_ROUTE_TILE 8
+
+int isdf_route_init(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, const int32_t* goals, int32_t n_goals, int32_t* dist,
+                    void* stream);
+
+/* up(4 * nx*ny*nz), up(x) = x rounded up to 256: one int32 volume, the ping-pong partner of dist.  ISDF_EINVAL for a side < 1 or
+ * more than ISDF_ROUTE_MAX_VOXELS voxels. */
+int64_t isdf_route_ws_bytes(int32_t nx, int32_t ny, int32_t nz);
+
+int isdf_route_relax(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, int32_t* dist, void* workspace,
+                     int64_t workspace_bytes, int32_t rounds, int32_t* changed, void* stream);
+
+int isdf_route_trace(const int32_t* dist, int32_t nx, int32_t ny, int32_t nz, const int32_t* starts, int32_t B, int32_t max_len,
+                     int32_t* path, int32_t* len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ SYMBOLS = [
     "isdf_traj_points", "isdf_traj_step",
     "isdf_tsdf_integrate", "isdf_edt_ws_bytes", "isdf_distance_transform", "isdf_occupancy_sdf",
     "isdf_tri_pack", "isdf_tri_ws_bytes", "isdf_tri_distance",
+    "isdf_route_init", "isdf_route_ws_bytes", "isdf_route_relax", "isdf_route_trace",
 ]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
@@ -168,6 +169,7 @@ TRAJ_RECORD = 16                                      # ISDF_TRAJ_RECORD (double
 TRAJ_MAX_WAYPOINTS, TRAJ_MAX_SPHERES, TRAJ_MAX_TRAJ = 1024, 32, 65536    # ISDF_TRAJ_MAX_*
 EDT_NONE, EDT_MAX_SIDE = 1 << 30, 1024                # ISDF_EDT_NONE, ISDF_EDT_MAX_SIDE
 TRI_TILE, TRI_SLOT_FLOATS, TRI_RECORD = 256, 24, 4   # ISDF_TRI_TILE, ISDF_TRI_SLOT_FLOATS, ISDF_TRI_RECORD (doubles)
+ROUTE_NONE, ROUTE_MAX_VOXELS, ROUTE_TILE = 1 << 30, 1 << 27, 8    # ISDF_ROUTE_NONE, ISDF_ROUTE_MAX_VOXELS, ISDF_ROUTE_TILE
 FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
 
 
@@ -257,6 +259,10 @@ def lib():
     L.isdf_tri_pack.argtypes = [vp, i64, vp, i64, P(f32), vp, i64, vp, vp]
     L.isdf_tri_ws_bytes.argtypes = [i64, i64]
     L.isdf_tri_distance.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.isdf_route_init.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
+    L.isdf_route_ws_bytes.argtypes = [i32, i32, i32]
+    L.isdf_route_relax.argtypes = [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp]
+    L.isdf_route_trace.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
     for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
         getattr(L, n).restype = C.c_int
     L.isdf_mesh_ws_bytes.restype = i64
@@ -265,6 +271,7 @@ def lib():
     L.isdf_pose_ws_bytes.restype = i64
     L.isdf_edt_ws_bytes.restype = i64
     L.isdf_tri_ws_bytes.restype = i64
+    L.isdf_route_ws_bytes.restype = i64
     if L.isdf_abi_version() != ABI_VERSION:
         raise IsdfError("libisdf_hip.so ABI %d != binding ABI %d" % (L.isdf_abi_version(), ABI_VERSION))
     _lib = L

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
-SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "fusion.hip", "tri.hip", "capi.hip"]
+SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "fusion.hip", "tri.hip", "route.hip", "capi.hip"]
 HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "block_reduce.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
@@ -45,6 +45,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 # (tsdf, weight) pair must equal an fp32 model bit for bit (every operation rounded, no fused multiply-add).
 # tri.hip: four query points against one triangle, the triangle the shared operand of the same refused form; closest point, squared
 # distance and index must equal an fp32 model bit for bit (every operation rounded, no fused multiply-add).
+# route.hip: int32 throughout, the default flags.
 PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"],
             "dw.hip": ["-fno-slp-vectorize"], "mesh.hip": ["-fno-slp-vectorize"],
             "render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "eval.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],

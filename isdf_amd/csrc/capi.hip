@@ -748,4 +748,35 @@ int isdf_tri_distance(const float* pts, int64_t n, const float* packed, int64_t 
   return launch_tri_distance(pts, n, packed, m, dist, index, closest, winding, record, workspace, (hipStream_t)stream);
 }
 
+// ---- routing through the map (route.hip)
+static bool route_dims_ok(int32_t nx, int32_t ny, int32_t nz) {
+  return nx >= 1 && ny >= 1 && nz >= 1 && (int64_t)nx * ny <= ISDF_ROUTE_MAX_VOXELS && (int64_t)nx * ny * nz <= ISDF_ROUTE_MAX_VOXELS;
+}
+
+int isdf_route_init(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, const int32_t* goals, int32_t n_goals, int32_t* dist,
+                    void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!free || !dist || !route_dims_ok(nx, ny, nz) || n_goals < 0 || (n_goals > 0 && !goals)) return ISDF_EINVAL;
+  return launch_route_init(free, nx, ny, nz, goals, n_goals, dist, (hipStream_t)stream);
+}
+
+int64_t isdf_route_ws_bytes(int32_t nx, int32_t ny, int32_t nz) {
+  return route_dims_ok(nx, ny, nz) ? route_volume_bytes(nx, ny, nz) : ISDF_EINVAL;
+}
+
+int isdf_route_relax(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, int32_t* dist, void* workspace,
+                     int64_t workspace_bytes, int32_t rounds, int32_t* changed, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!free || !dist || !changed || !route_dims_ok(nx, ny, nz) || rounds < 1) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_route_ws_bytes(nx, ny, nz)) return ISDF_EWORKSPACE;
+  return launch_route_relax(free, nx, ny, nz, dist, (int32_t*)workspace, rounds, changed, (hipStream_t)stream);
+}
+
+int isdf_route_trace(const int32_t* dist, int32_t nx, int32_t ny, int32_t nz, const int32_t* starts, int32_t B, int32_t max_len,
+                     int32_t* path, int32_t* len, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!dist || !starts || !path || !len || !route_dims_ok(nx, ny, nz) || B < 0 || max_len < 1) return ISDF_EINVAL;
+  return launch_route_trace(dist, nx, ny, nz, starts, B, max_len, path, len, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -74,5 +74,12 @@ int launch_tri_pack(const float* verts, int64_t nv, const int32_t* faces, int64_
                     hipStream_t st);
 int launch_tri_distance(const float* pts, int64_t n, const float* packed, int64_t m, float* dist, int32_t* index, float* closest,
                         float* winding, double* record, void* workspace, hipStream_t st);
+int launch_route_init(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, const int32_t* goals, int32_t n_goals, int32_t* dist,   // route.hip
+                      hipStream_t st);
+int64_t route_volume_bytes(int32_t nx, int32_t ny, int32_t nz);
+int launch_route_relax(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, int32_t* dist, int32_t* ws, int32_t rounds,
+                       int32_t* changed, hipStream_t st);
+int launch_route_trace(const int32_t* dist, int32_t nx, int32_t ny, int32_t nz, const int32_t* starts, int32_t B, int32_t max_len,
+                       int32_t* path, int32_t* len, hipStream_t st);
 
 }  // namespace isdf

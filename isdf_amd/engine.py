@@ -876,6 +876,79 @@ class Engine:
                                                int(ws.numel()), _stream(self.device)), "isdf_occupancy_sdf")
         return out
 
+    # ---- routing through the map: geodesic field and path ---------------------------------
+    def _route_volume(self, name, what, t, dtype):
+        """(t, dims): `t` checked to be a contiguous `dtype` [nx, ny, nz] volume on this device, every side >= 1"""
+        if not torch.is_tensor(t) or t.dim() != 3 or min(t.shape) < 1 or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s [nx, ny, nz] tensor with every side >= 1" % (name, what, dtype))
+        self._check_device(name, what, t)
+        dims = tuple(int(v) for v in t.shape)
+        if dims[0] * dims[1] * dims[2] > _ffi.ROUTE_MAX_VOXELS:
+            raise ValueError("%s: at most 2^27 voxels (got %s)" % (name, dims))
+        return t, dims
+
+    def _route_voxels(self, name, what, v):
+        """voxel coordinates as a contiguous int32 [n, 3] tensor on this device"""
+        v = torch.as_tensor(v)
+        if v.dtype.is_floating_point or v.dtype == torch.bool or v.numel() % 3 != 0:
+            raise ValueError("%s: %s must be integer voxel coordinates [n, 3]" % (name, what))
+        return v.detach().reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
+
+    def route_init(self, free, goals, out=None):
+        """dist int32 [nx,ny,nz] on the device: isdf_route_init -- _ffi.ROUTE_NONE (2^30) everywhere, 0 at every goal (integer voxel
+        coordinates [n,3], n = 0 allowed) that is inside the grid and free.  free: contiguous uint8 [nx,ny,nz] on this device,
+        non-zero = free.  out: a dist volume to overwrite.  No host synchronisation."""
+        f, dims = self._route_volume("route_init", "free", free, torch.uint8)
+        g = self._route_voxels("route_init", "goals", goals)
+        if out is None:
+            out = torch.empty(dims, dtype=torch.int32, device=self.device)
+        elif self._route_volume("route_init", "out", out, torch.int32)[1] != dims:
+            raise ValueError("route_init: out is %s, free %s" % (tuple(out.shape), dims))
+        _ffi.check(self.lib.isdf_route_init(_ffi.ptr(f), dims[0], dims[1], dims[2], _addr(g), int(g.shape[0]), _ffi.ptr(out),
+                                            _stream(self.device)), "isdf_route_init")
+        return out
+
+    def route_relax(self, free, dist, rounds=1, changed=None):
+        """changed int32 [rounds] on the device: isdf_route_relax -- `rounds` rounds (two tile launches each) of the 26-neighbour
+        <3,4,5> chamfer relaxation on `dist` IN PLACE (int32 [nx,ny,nz] from route_init on the same `free`); changed[r] = 1 iff
+        round r lowered any voxel.  Once a round changes nothing, dist is the exact shortest-path distance to the nearest goal.
+        changed: an int32 tensor of at least `rounds` elements to reuse.  The workspace is kept across calls.  No host
+        synchronisation: the caller decides when to look (isdf_amd.routing.distance_field does)."""
+        f, dims = self._route_volume("route_relax", "free", free, torch.uint8)
+        if self._route_volume("route_relax", "dist", dist, torch.int32)[1] != dims:
+            raise ValueError("route_relax: dist is %s, free %s" % (tuple(dist.shape), dims))
+        rounds = int(rounds)
+        if rounds < 1:
+            raise ValueError("route_relax: rounds >= 1 (got %d)" % rounds)
+        if changed is None:
+            changed = torch.empty(rounds, dtype=torch.int32, device=self.device)
+        elif changed.dtype != torch.int32 or changed.numel() < rounds or not changed.is_contiguous():
+            raise ValueError("route_relax: changed must be a contiguous int32 tensor of at least %d elements" % rounds)
+        else:
+            self._check_device("route_relax", "changed", changed)
+        ws = self._scratch("route", int(self.lib.isdf_route_ws_bytes(*dims)))
+        _ffi.check(self.lib.isdf_route_relax(_ffi.ptr(f), dims[0], dims[1], dims[2], _ffi.ptr(dist), _ffi.ptr(ws), int(ws.numel()),
+                                             rounds, _ffi.ptr(changed), _stream(self.device)), "isdf_route_relax")
+        return changed.reshape(-1)[:rounds]
+
+    def route_trace(self, dist, starts, max_len):
+        """(path int32 [B, max_len], len int32 [B]) on the device: isdf_route_trace -- from every start (integer voxel coordinates
+        [B,3]) down `dist` to a goal, at every voxel to the first neighbour, in lexicographic (di, dj, dk) order, that explains
+        its distance.  path holds linear voxel indices (i * ny + j) * nz + k, len the number of voxels with both ends; 0 for a
+        start that is outside, blocked or unreachable, -1 where max_len is too small or the field is not converged.  Entries of
+        path beyond len are not written.  No host synchronisation."""
+        d, dims = self._route_volume("route_trace", "dist", dist, torch.int32)
+        s = self._route_voxels("route_trace", "starts", starts)
+        B, max_len = int(s.shape[0]), int(max_len)
+        if max_len < 1:
+            raise ValueError("route_trace: max_len >= 1 (got %d)" % max_len)
+        path = torch.empty(B, max_len, dtype=torch.int32, device=self.device)
+        length = torch.empty(B, dtype=torch.int32, device=self.device)
+        if B:
+            _ffi.check(self.lib.isdf_route_trace(_ffi.ptr(d), dims[0], dims[1], dims[2], _ffi.ptr(s), B, max_len, _ffi.ptr(path),
+                                                 _ffi.ptr(length), _stream(self.device)), "isdf_route_trace")
+        return path, length
+
     # ---- ground truth from a triangle mesh ------------------------------------------------
     def tri_pack(self, vertices, faces, transform=None):
         """(packed f32 [slots, 24], counts i32 [2], m) on the device: isdf_tri_pack, the mesh gathered once into the layout
