@@ -13,24 +13,6 @@ LIB_PATH = os.environ.get("ISDF_HIP_LIB") or os.path.join(HERE, "libisdf_hip.so"
 
 ABI_VERSION = 8
 
-# every symbol include/isdf_hip.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    "isdf_abi_version", "isdf_error_string", "isdf_check_net", "isdf_param_count", "isdf_shadow_bytes",
-    "isdf_workspace_bytes", "isdf_reduce_floats", "isdf_reduce_split_floats", "isdf_sample_scan_bytes", "isdf_pack_weights",
-    "isdf_sample_rays",
-    "isdf_sdf_eval", "isdf_train_step", "isdf_train_step_adamw", "isdf_train_step_finish", "isdf_bounds_pc",
-    "isdf_frame_avg", "isdf_adamw", "isdf_estimate_normals", "isdf_render_depth", "isdf_allreduce_sum_f32",
-    "isdf_mesh_ws_bytes", "isdf_marching_cubes", "isdf_mc_tables", "isdf_render_ws_bytes", "isdf_render_views",
-    "isdf_sdf_metrics", "isdf_nn_distance", "isdf_slice_images", "isdf_plane_points", "isdf_region_metrics",
-    "isdf_visible_points",
-    "isdf_band_ws_bytes", "isdf_band_begin", "isdf_band_select", "isdf_band_emit", "isdf_band_update", "isdf_band_leaks",
-    "isdf_grid_points",
-    "isdf_pose_ws_bytes", "isdf_pose_points", "isdf_pose_system",
-    "isdf_traj_points", "isdf_traj_step",
-    "isdf_tsdf_integrate", "isdf_edt_ws_bytes", "isdf_distance_transform", "isdf_occupancy_sdf",
-    "isdf_tri_pack", "isdf_tri_ws_bytes", "isdf_tri_distance",
-    "isdf_route_init", "isdf_route_ws_bytes", "isdf_route_relax", "isdf_route_trace",
-]
 MC_MAX_TRIS = 5      # ISDF_MC_MAX_TRIS
 
 LS_SDF, LS_GRAD, LS_EIK, LS_TOTAL, LS_COUNT = 0, 1, 2, 3, 4
@@ -183,6 +165,77 @@ def tri_packed_bytes(m):
     return (int(m) + TRI_TILE - 1) // TRI_TILE * TRI_TILE * TRI_SLOT_FLOATS * 4
 
 
+P, i32, i64, f32, vp = C.POINTER, C.c_int32, C.c_int64, C.c_float, C.c_void_p
+
+# the C struct names of include/isdf_hip.h -> their mirrors above
+STRUCTS = {"isdf_net_cfg": NetCfg, "isdf_sample_args": SampleArgs, "isdf_sample_out": SampleOut, "isdf_loss_cfg": LossCfg,
+           "isdf_step_args": StepArgs, "isdf_step_out": StepOut, "isdf_optim_args": OptimArgs, "isdf_mc_args": McArgs,
+           "isdf_render_args": RenderArgs, "isdf_gt_volume": GtVolumeArgs, "isdf_region_args": RegionArgs,
+           "isdf_colormap": ColormapArgs, "isdf_band_args": BandArgs, "isdf_pose_args": PoseArgs, "isdf_traj_args": TrajArgs,
+           "isdf_tsdf_args": TsdfArgs}
+
+# every function include/isdf_hip.h declares, in header order: name -> (restype, argtypes).  This is the one place a function is
+# declared on the Python side; tests/test_abi.py holds every line (and STRUCTS, and the constants above) to the header.
+PROTOTYPES = {
+    "isdf_abi_version": (C.c_int, []),
+    "isdf_error_string": (C.c_char_p, [C.c_int]),
+    "isdf_check_net": (C.c_int, [P(NetCfg)]),
+    "isdf_param_count": (i64, [P(NetCfg)]),
+    "isdf_shadow_bytes": (i64, [P(NetCfg)]),
+    "isdf_workspace_bytes": (i64, [P(NetCfg), i64, i32]),
+    "isdf_reduce_floats": (i64, [P(NetCfg), i32]),
+    "isdf_reduce_split_floats": (i64, [P(NetCfg)]),
+    "isdf_pack_weights": (C.c_int, [P(NetCfg), vp, vp, vp]),
+    "isdf_sample_scan_bytes": (i64, [i64]),
+    "isdf_sample_rays": (C.c_int, [P(SampleArgs), P(SampleOut), vp, i64, vp]),
+    "isdf_sdf_eval": (C.c_int, [P(NetCfg), vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]),
+    "isdf_train_step": (C.c_int, [P(NetCfg), P(LossCfg), vp, vp, P(StepArgs), P(StepOut), vp, i64, vp]),
+    "isdf_train_step_adamw": (C.c_int, [P(NetCfg), P(LossCfg), P(StepArgs), P(StepOut), P(OptimArgs), vp, i64, vp]),
+    "isdf_train_step_finish": (C.c_int, [P(NetCfg), P(OptimArgs), vp, i32, i32, vp, vp]),
+    "isdf_allreduce_sum_f32": (C.c_int, [vp, vp, vp, i64, vp]),
+    "isdf_bounds_pc": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]),
+    "isdf_frame_avg": (C.c_int, [vp, i64, i32, vp, vp, vp, vp]),
+    "isdf_estimate_normals": (C.c_int, [vp, i32, i32, f32, f32, f32, f32, vp, vp]),
+    "isdf_render_depth": (C.c_int, [vp, i64, i64, i32, vp, vp, vp, f32, vp, vp, vp]),
+    "isdf_adamw": (C.c_int, [P(NetCfg), vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp]),
+    "isdf_mesh_ws_bytes": (i64, [i32, i32, i32]),
+    "isdf_marching_cubes": (C.c_int, [P(McArgs), vp, vp, vp, i64, vp, i64, vp, i64, vp]),
+    "isdf_mc_tables": (C.c_int, [vp, vp]),
+    "isdf_render_ws_bytes": (i64, [P(NetCfg), i32, i32, i32, i32]),
+    "isdf_render_views": (C.c_int, [P(NetCfg), vp, vp, P(RenderArgs), vp, vp, vp, i64, vp]),
+    "isdf_sdf_metrics": (C.c_int, [P(GtVolumeArgs), vp, vp, i64, i32, f32, vp, vp, vp, vp, i64, vp]),
+    "isdf_region_metrics": (C.c_int, [P(RegionArgs), vp, vp, i64, vp]),
+    "isdf_nn_distance": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]),
+    "isdf_slice_images": (C.c_int, [vp, vp, i64, P(ColormapArgs), P(GtVolumeArgs), f32, f32, vp, vp, vp, vp, vp, vp]),
+    "isdf_plane_points": (C.c_int, [P(f32), P(f32), P(f32), i32, i32, vp, vp]),
+    "isdf_visible_points": (C.c_int, [vp, i64, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    "isdf_band_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "isdf_band_begin": (C.c_int, [P(BandArgs), vp, vp]),
+    "isdf_band_select": (C.c_int, [P(BandArgs), i32, vp, vp, vp, i64, vp]),
+    "isdf_band_emit": (C.c_int, [P(BandArgs), i32, vp, vp, vp, i64, vp, i64, vp]),
+    "isdf_band_update": (C.c_int, [P(BandArgs), i32, vp, vp, vp, i64, vp, vp, i64, vp]),
+    "isdf_band_leaks": (C.c_int, [P(BandArgs), vp, vp, vp, i64, vp]),
+    "isdf_grid_points": (C.c_int, [i32, i32, i32, P(f32), vp, vp]),
+    "isdf_pose_ws_bytes": (i64, [i32]),
+    "isdf_pose_points": (C.c_int, [P(PoseArgs), vp, vp]),
+    "isdf_pose_system": (C.c_int, [P(PoseArgs), vp, vp, vp, f32, f32, vp, vp, i64, vp]),
+    "isdf_traj_points": (C.c_int, [P(TrajArgs), vp, vp]),
+    "isdf_traj_step": (C.c_int, [P(TrajArgs), vp, vp, vp, vp, vp, vp]),
+    "isdf_tsdf_integrate": (C.c_int, [P(TsdfArgs), vp]),
+    "isdf_edt_ws_bytes": (i64, [i32, i32, i32]),
+    "isdf_distance_transform": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i64, vp]),
+    "isdf_occupancy_sdf": (C.c_int, [vp, i32, i32, i32, C.c_double, vp, vp, i64, vp]),
+    "isdf_tri_pack": (C.c_int, [vp, i64, vp, i64, P(f32), vp, i64, vp, vp]),
+    "isdf_tri_ws_bytes": (i64, [i64, i64]),
+    "isdf_tri_distance": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "isdf_route_init": (C.c_int, [vp, i32, i32, i32, vp, i32, vp, vp]),
+    "isdf_route_ws_bytes": (i64, [i32, i32, i32]),
+    "isdf_route_relax": (C.c_int, [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp]),
+    "isdf_route_trace": (C.c_int, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
+}
+SYMBOLS = list(PROTOTYPES)
+
+
 class IsdfError(RuntimeError):
     pass
 
@@ -202,76 +255,9 @@ def lib():
     # process holds two HIP runtimes (torch asks for the unversioned name), and the library's own finds no device next to torch's.
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    P, i32, i64, f32, vp = C.POINTER, C.c_int32, C.c_int64, C.c_float, C.c_void_p
-    L.isdf_abi_version.restype = C.c_int
-    L.isdf_error_string.restype = C.c_char_p
-    L.isdf_error_string.argtypes = [C.c_int]
-    L.isdf_check_net.restype = C.c_int
-    L.isdf_check_net.argtypes = [P(NetCfg)]
-    for n in ("isdf_param_count", "isdf_shadow_bytes", "isdf_reduce_split_floats"):
-        getattr(L, n).restype = i64
-        getattr(L, n).argtypes = [P(NetCfg)]
-    L.isdf_workspace_bytes.restype = i64
-    L.isdf_workspace_bytes.argtypes = [P(NetCfg), i64, i32]
-    L.isdf_reduce_floats.restype = i64
-    L.isdf_reduce_floats.argtypes = [P(NetCfg), i32]
-    L.isdf_pack_weights.argtypes = [P(NetCfg), vp, vp, vp]
-    L.isdf_sample_scan_bytes.restype = i64
-    L.isdf_sample_scan_bytes.argtypes = [i64]
-    L.isdf_sample_rays.argtypes = [P(SampleArgs), P(SampleOut), vp, i64, vp]
-    L.isdf_sdf_eval.argtypes = [P(NetCfg), vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    L.isdf_train_step.argtypes = [P(NetCfg), P(LossCfg), vp, vp, P(StepArgs), P(StepOut), vp, i64, vp]
-    L.isdf_train_step_adamw.argtypes = [P(NetCfg), P(LossCfg), P(StepArgs), P(StepOut), P(OptimArgs), vp, i64, vp]
-    L.isdf_train_step_finish.argtypes = [P(NetCfg), P(OptimArgs), vp, i32, i32, vp, vp]
-    L.isdf_allreduce_sum_f32.argtypes = [vp, vp, vp, C.c_int64, vp]
-    L.isdf_bounds_pc.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
-    L.isdf_frame_avg.argtypes = [vp, i64, i32, vp, vp, vp, vp]
-    L.isdf_adamw.argtypes = [P(NetCfg), vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp, vp]
-    L.isdf_estimate_normals.argtypes = [vp, i32, i32, f32, f32, f32, f32, vp, vp]
-    L.isdf_render_depth.argtypes = [vp, i64, i64, i32, vp, vp, vp, f32, vp, vp, vp]
-    L.isdf_mesh_ws_bytes.argtypes = [i32, i32, i32]
-    L.isdf_marching_cubes.argtypes = [P(McArgs), vp, vp, vp, i64, vp, i64, vp, i64, vp]
-    L.isdf_mc_tables.argtypes = [vp, vp]
-    L.isdf_render_ws_bytes.argtypes = [P(NetCfg), i32, i32, i32, i32]
-    L.isdf_render_views.argtypes = [P(NetCfg), vp, vp, P(RenderArgs), vp, vp, vp, i64, vp]
-    L.isdf_sdf_metrics.argtypes = [P(GtVolumeArgs), vp, vp, i64, i32, f32, vp, vp, vp, vp, i64, vp]
-    L.isdf_nn_distance.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]
-    L.isdf_slice_images.argtypes = [vp, vp, i64, P(ColormapArgs), P(GtVolumeArgs), f32, f32, vp, vp, vp, vp, vp, vp]
-    L.isdf_plane_points.argtypes = [P(f32), P(f32), P(f32), i32, i32, vp, vp]
-    L.isdf_region_metrics.argtypes = [P(RegionArgs), vp, vp, i64, vp]
-    L.isdf_visible_points.argtypes = [vp, i64, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp]
-    L.isdf_band_ws_bytes.argtypes = [i32, i32, i32, i32]
-    L.isdf_band_begin.argtypes = [P(BandArgs), vp, vp]
-    L.isdf_band_select.argtypes = [P(BandArgs), i32, vp, vp, vp, i64, vp]
-    L.isdf_band_emit.argtypes = [P(BandArgs), i32, vp, vp, vp, i64, vp, i64, vp]
-    L.isdf_band_update.argtypes = [P(BandArgs), i32, vp, vp, vp, i64, vp, vp, i64, vp]
-    L.isdf_band_leaks.argtypes = [P(BandArgs), vp, vp, vp, i64, vp]
-    L.isdf_grid_points.argtypes = [i32, i32, i32, P(f32), vp, vp]
-    L.isdf_pose_ws_bytes.argtypes = [i32]
-    L.isdf_pose_points.argtypes = [P(PoseArgs), vp, vp]
-    L.isdf_pose_system.argtypes = [P(PoseArgs), vp, vp, vp, f32, f32, vp, vp, i64, vp]
-    L.isdf_traj_points.argtypes = [P(TrajArgs), vp, vp]
-    L.isdf_traj_step.argtypes = [P(TrajArgs), vp, vp, vp, vp, vp, vp]
-    L.isdf_tsdf_integrate.argtypes = [P(TsdfArgs), vp]
-    L.isdf_edt_ws_bytes.argtypes = [i32, i32, i32]
-    L.isdf_distance_transform.argtypes = [vp, i32, i32, i32, i32, vp, vp, i64, vp]
-    L.isdf_occupancy_sdf.argtypes = [vp, i32, i32, i32, C.c_double, vp, vp, i64, vp]
-    L.isdf_tri_pack.argtypes = [vp, i64, vp, i64, P(f32), vp, i64, vp, vp]
-    L.isdf_tri_ws_bytes.argtypes = [i64, i64]
-    L.isdf_tri_distance.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]
-    L.isdf_route_init.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
-    L.isdf_route_ws_bytes.argtypes = [i32, i32, i32]
-    L.isdf_route_relax.argtypes = [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp]
-    L.isdf_route_trace.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
-    for n in SYMBOLS[SYMBOLS.index("isdf_pack_weights"):]:
-        getattr(L, n).restype = C.c_int
-    L.isdf_mesh_ws_bytes.restype = i64
-    L.isdf_render_ws_bytes.restype = i64
-    L.isdf_band_ws_bytes.restype = i64
-    L.isdf_pose_ws_bytes.restype = i64
-    L.isdf_edt_ws_bytes.restype = i64
-    L.isdf_tri_ws_bytes.restype = i64
-    L.isdf_route_ws_bytes.restype = i64
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.isdf_abi_version() != ABI_VERSION:
         raise IsdfError("libisdf_hip.so ABI %d != binding ABI %d" % (L.isdf_abi_version(), ABI_VERSION))
     _lib = L

@@ -1,17 +1,14 @@
-"""CPU-side checks of the C-ABI library: it loads, exports every symbol
-include/isdf_hip.h declares, and its size queries (pure host code) are right.
-No kernel is launched here."""
+"""CPU-side checks of the C-ABI library.  The first three tests hold the whole Python side of the boundary (isdf_amd/_ffi.py:
+PROTOTYPES, STRUCTS and the constants) to include/isdf_hip.h, table-driven through tests/abi_util.py; the rest check that the
+library loads and that its size queries (pure host code) are right.  No kernel is launched here."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
 import pytest
 
 from isdf_amd import _ffi, build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import abi_util as au
 
 
 @pytest.fixture(scope="module")
@@ -20,19 +17,63 @@ def lib():
     return _ffi.lib()
 
 
-def test_header_symbols_all_exported(lib):
-    hdr = open(os.path.join(ROOT, "include", "isdf_hip.h")).read()
-    declared = sorted(set(re.findall(r"\b(isdf_[a-z_0-9]+)\s*\(", hdr)))
-    assert declared == sorted(_ffi.SYMBOLS)
-    for s in declared:
-        assert hasattr(lib, s), s
+def test_every_prototype_is_bound_as_the_header_declares_it(lib):
+    """all functions of the header: declared, exported, and bound in _ffi.PROTOTYPES with the restype and every argtype the
+    header's C types require (abi_util.bindings)"""
+    declared = au.prototypes()
+    assert list(declared) == _ffi.SYMBOLS and len(declared) >= 55
+    for name, (ret, params) in declared.items():
+        fn = getattr(lib, name)
+        assert fn.restype in au.bindings(ret, _ffi.STRUCTS), (name, ret, fn.restype)
+        assert len(fn.argtypes) == len(params), name
+        for k, (c_type, bound) in enumerate(zip(params, fn.argtypes)):
+            assert bound in au.bindings(c_type, _ffi.STRUCTS), (name, k, c_type, bound)
+
+
+def test_ctypes_structs_match_the_header_layout(tmp_path):
+    """every struct that crosses the boundary: the mirror in _ffi.STRUCTS names the header's fields in the header's order, and its
+    size and every field offset are what gcc makes of include/isdf_hip.h (a silent mismatch would hand the kernels shifted
+    pointers)"""
+    assert au.struct_fields("isdf_tsdf_args")[:8] == ["nx", "ny", "nz", "F", "H", "W", "origin", "spacing"]     # the parser itself:
+    assert au.struct_fields("isdf_gt_volume") == ["values", "nx", "ny", "nz", "reserved", "spacing", "origin"]  # commas and arrays
+    assert au.struct_fields("isdf_step_out")[4:6] == ["prof_events", "host_mailbox"]                            # void**
+    assert sorted(au.struct_names()) == sorted(_ffi.STRUCTS) and len(_ffi.STRUCTS) >= 16
+    sizes, offsets, _ = au.probe(tmp_path, structs=_ffi.STRUCTS)
+    for name, ct in _ffi.STRUCTS.items():
+        fields = [f for f, _ in ct._fields_]
+        assert fields == au.struct_fields(name), name
+        assert C.sizeof(ct) == sizes[name], name
+        assert {f: getattr(ct, f).offset for f in fields} == offsets[name], name
+
+
+# upper-case integers of _ffi that the header does not define: the bits of isdf_region_args.flags, which it documents in prose
+NOT_IN_HEADER = {"FLAG_VIS_SDF", "FLAG_VOX_SDF", "FLAG_VIS_GRAD", "FLAG_VOX_GRAD"}
+MIRRORED = {"ABI_VERSION", "MC_MAX_TRIS", "LS_SDF", "LS_GRAD", "LS_EIK", "LS_TOTAL", "LS_COUNT", "MAX_INLINE_FRAMES", "RANGE_SCALAR",
+            "RANGE_DEPTH", "RANGE_UPSAMPLE", "COLORMAP_MAX_COLORS", "METRICS_RECORD", "SDF_METRICS_WS_BYTES", "REGION_RECORD",
+            "REGION_METRICS_WS_BYTES", "POSE_RECORD", "POSE_MAX_BLOCKS", "TRAJ_RECORD", "TRAJ_MAX_WAYPOINTS", "TRAJ_MAX_SPHERES",
+            "TRAJ_MAX_TRAJ", "EDT_NONE", "EDT_MAX_SIDE", "TRI_TILE", "TRI_SLOT_FLOATS", "TRI_RECORD", "ROUTE_NONE", "ROUTE_MAX_VOXELS",
+            "ROUTE_TILE"}
+
+
+def test_constants_and_size_macros_equal_the_header_s(tmp_path):
+    """every upper-case integer X of _ffi equals ISDF_X (a macro or an enumerator) as gcc evaluates it, or is on NOT_IN_HEADER;
+    the set that is compared never shrinks; the two size functions equal the header's function-like macros"""
+    header = set(au.constant_names())
+    mine = {k: v for k, v in vars(_ffi).items() if k.isupper() and type(v) is int}
+    matched = {k for k in mine if "ISDF_" + k in header}
+    assert set(mine) - matched == NOT_IN_HEADER
+    assert matched >= MIRRORED
+    sizes = (0, 1, 256, 257, 200000)
+    macros = ["ISDF_NN_WS_BYTES(%d)" % n for n in sizes] + ["ISDF_TRI_PACKED_BYTES(%d)" % n for n in sizes]
+    _, _, values = au.probe(tmp_path, constants=["ISDF_" + k for k in sorted(matched)], macros=macros)
+    assert {k: mine[k] for k in matched} == {k: values["ISDF_" + k] for k in matched}
+    for n in sizes:
+        assert _ffi.nn_ws_bytes(n) == values["ISDF_NN_WS_BYTES(%d)" % n], n
+        assert _ffi.tri_packed_bytes(n) == values["ISDF_TRI_PACKED_BYTES(%d)" % n], n
 
 
 def test_abi_version_and_errors(lib):
-    import re
-    from isdf_amd import _ffi
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "isdf_hip.h")).read()
-    assert lib.isdf_abi_version() == _ffi.ABI_VERSION == int(re.search(r"#define ISDF_ABI_VERSION (\d+)", hdr).group(1))
+    assert lib.isdf_abi_version() == _ffi.ABI_VERSION
     assert lib.isdf_error_string(0) == b"ok"
     assert b"invalid" in lib.isdf_error_string(-1)
 
@@ -88,31 +129,6 @@ def test_engine_refuses_cpu():
     from isdf_amd.engine import Engine, NetConfig
     with pytest.raises(_ffi.IsdfError):
         Engine(NetConfig(), "cpu")
-
-
-def test_ctypes_structs_match_the_header_layout(tmp_path):
-    """sizeof / offsetof of every struct that crosses the boundary, as gcc lays out include/isdf_hip.h, against the ctypes
-    mirrors in isdf_amd/_ffi.py (a silent mismatch would hand the kernels shifted pointers)"""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    structs = {"isdf_net_cfg": _ffi.NetCfg, "isdf_sample_args": _ffi.SampleArgs, "isdf_sample_out": _ffi.SampleOut,
-               "isdf_loss_cfg": _ffi.LossCfg, "isdf_step_args": _ffi.StepArgs, "isdf_step_out": _ffi.StepOut,
-               "isdf_optim_args": _ffi.OptimArgs}
-    last = {"isdf_net_cfg": "spill_operand", "isdf_sample_args": "n_inline", "isdf_sample_out": "pc", "isdf_loss_cfg": "orien_loss",
-            "isdf_step_args": "extra_value", "isdf_step_out": "split_event", "isdf_optim_args": "frame_avg_inline_n"}
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "isdf_hip.h"', 'int main(void) {']
-    for name in structs:
-        src.append('  printf("%s %%zu %%zu\\n", sizeof(%s), offsetof(%s, %s));' % (name, name, name, last[name]))
-    src += ['  return 0;', '}']
-    c = tmp_path / "sizes.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(c), "-o", str(exe)])
-    for line in subprocess.check_output([str(exe)], text=True).splitlines():
-        name, size, off = line.split()
-        ct = structs[name]
-        assert C.sizeof(ct) == int(size), (name, C.sizeof(ct), size)
-        assert getattr(ct, last[name]).offset == int(off), (name, last[name])
 
 
 def test_allreduce_entry_point_checks_its_arguments_and_reports_a_refusing_collective():

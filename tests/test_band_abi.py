@@ -99,17 +99,3 @@ def test_missing_or_small_workspace_is_eworkspace(lib):
         rc = _calls(lib, _args(), ws=ws, wsn=wsn)
         assert rc[1:] == [EWORKSPACE] * 4, (ws, wsn)
     assert lib.isdf_band_emit(C.byref(_args()), 8, 0x1000, None, None, 0, None, 0, None) == 0        # an empty list is a no-op
-
-
-def test_ctypes_struct_matches_the_header_layout(tmp_path):
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    c = tmp_path / "sizes.c"
-    c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "isdf_hip.h"\nint main(void) {\n'
-                 '  printf("%zu %zu %zu\\n", sizeof(isdf_band_args), offsetof(isdf_band_args, index_to_world), '
-                 'offsetof(isdf_band_args, points));\n  return 0;\n}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(c), "-o", str(exe)])
-    size, off_a, off_p = (int(x) for x in subprocess.check_output([str(exe)], text=True).split())
-    assert (C.sizeof(_ffi.BandArgs), _ffi.BandArgs.index_to_world.offset, _ffi.BandArgs.points.offset) == (size, off_a, off_p)

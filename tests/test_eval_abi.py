@@ -1,17 +1,9 @@
-"""C ABI of the evaluation entry points: the header declares isdf_sdf_metrics / isdf_nn_distance, the built library exports
-them, isdf_amd/_ffi.py binds them with matching argument types, isdf_gt_volume's layout and the size macros match what the host
-C compiler makes of the header, and bad arguments are refused before anything is launched (no GPU needed)."""
+"""C ABI of the evaluation entry points: isdf_sdf_metrics / isdf_nn_distance keep their parameter counts, and bad arguments are
+refused before anything is launched (no GPU needed).  What the header says of their types, of isdf_gt_volume's layout and of the
+size macros is held to isdf_amd/_ffi.py by tests/test_abi.py."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIELDS = ["values", "nx", "ny", "nz", "reserved", "spacing", "origin"]
-C_TYPES = {"const isdf_gt_volume*": "P(GtVolumeArgs)", "const float*": "vp", "float*": "vp", "double*": "vp", "uint8_t*": "vp",
-           "int32_t*": "vp", "void*": "vp", "int64_t": "i64", "int32_t": "i32", "float": "f32"}
 
 
 @pytest.fixture(scope="module")
@@ -21,43 +13,11 @@ def lib():
     return _ffi.lib()
 
 
-def _declared(name):
-    hdr = open(os.path.join(ROOT, "include", "isdf_hip.h")).read()
-    m = re.search(r"\bint %s\(([^;]*?)\);" % name, hdr, re.S)
-    assert m, name + " is not declared in include/isdf_hip.h"
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
-    return [a.rsplit(" ", 1)[0] for a in args]            # the types, parameter names dropped
-
-
 def test_header_declares_library_exports_and_ffi_binds_with_matching_types(lib):
     from isdf_amd import _ffi
-    P, i32, i64, f32, vp = C.POINTER, C.c_int32, C.c_int64, C.c_float, C.c_void_p
-    names = {"P(GtVolumeArgs)": P(_ffi.GtVolumeArgs), "vp": vp, "i64": i64, "i32": i32, "f32": f32}
     for fn in ("isdf_sdf_metrics", "isdf_nn_distance"):
         assert fn in _ffi.SYMBOLS and hasattr(lib, fn)
-        want = [names[C_TYPES[t]] for t in _declared(fn)]
-        assert list(getattr(lib, fn).argtypes) == want, fn
-        assert getattr(lib, fn).restype is C.c_int
-    assert len(_declared("isdf_sdf_metrics")) == 12 and len(_declared("isdf_nn_distance")) == 10
-
-
-def test_gt_volume_layout_and_size_macros_match_the_header(tmp_path, lib):
-    from isdf_amd import _ffi
-    c = tmp_path / "gv.c"
-    body = "".join('  printf("%%zu\\n", offsetof(isdf_gt_volume, %s));\n' % f for f in FIELDS)
-    c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "isdf_hip.h"\nint main(void) {\n'
-                 '  printf("%zu\\n", sizeof(isdf_gt_volume));\n' + body +
-                 '  printf("%d %d %lld %lld %lld\\n", ISDF_METRICS_RECORD, (int)ISDF_SDF_METRICS_WS_BYTES,\n'
-                 '         (long long)ISDF_NN_WS_BYTES(0), (long long)ISDF_NN_WS_BYTES(257), (long long)ISDF_NN_WS_BYTES(200000));\n'
-                 '  return 0;\n}\n')
-    exe = tmp_path / "gv"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)], text=True).split()
-    assert C.sizeof(_ffi.GtVolumeArgs) == int(out[0])
-    assert [getattr(_ffi.GtVolumeArgs, f).offset for f in FIELDS] == [int(x) for x in out[1:1 + len(FIELDS)]]
-    assert [f for f, _ in _ffi.GtVolumeArgs._fields_] == FIELDS
-    assert [int(x) for x in out[-5:]] == [_ffi.METRICS_RECORD, _ffi.SDF_METRICS_WS_BYTES, _ffi.nn_ws_bytes(0), _ffi.nn_ws_bytes(257),
-                                          _ffi.nn_ws_bytes(200000)]
+    assert len(lib.isdf_sdf_metrics.argtypes) == 12 and len(lib.isdf_nn_distance.argtypes) == 10
 
 
 def test_argument_checks_refuse_before_any_launch(lib):

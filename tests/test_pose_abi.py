@@ -1,8 +1,6 @@
 """CPU-side checks of the pose-alignment entry points (include/isdf_hip.h): exported, the ABI version unchanged, the workspace size
-as documented, the struct laid out as the header's, and every invalid argument refused before anything is launched."""
+as documented, and every invalid argument refused before anything is launched."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -101,19 +99,3 @@ def test_missing_or_small_workspace_is_eworkspace(lib):
     need = lib.isdf_pose_ws_bytes(2)
     for ws, wsn in ((None, need), (ADDR, need - 1), (ADDR, 0)):
         assert _calls(lib, _args(), ws=ws, wsn=wsn)[1] == EWORKSPACE, (ws, wsn)
-
-
-def test_ctypes_struct_matches_the_header_layout(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    fields = [name for name, _ in _ffi.PoseArgs._fields_]
-    c = tmp_path / "sizes.c"
-    c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "isdf_hip.h"\nint main(void) {\n'
-                 '  printf("%zu\\n", sizeof(isdf_pose_args));\n'
-                 + "".join('  printf("%%zu\\n", offsetof(isdf_pose_args, %s));\n' % f for f in fields)
-                 + '  printf("%d %d\\n", ISDF_POSE_RECORD, ISDF_POSE_MAX_BLOCKS);\n  return 0;\n}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(c), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)], text=True).split()
-    assert C.sizeof(_ffi.PoseArgs) == int(out[0])
-    assert [getattr(_ffi.PoseArgs, f).offset for f in fields] == [int(x) for x in out[1:1 + len(fields)]]
-    assert (_ffi.POSE_RECORD, _ffi.POSE_MAX_BLOCKS) == (int(out[-2]), int(out[-1])) == (32, 64)
