@@ -831,6 +831,98 @@ int isdf_traj_points(const isdf_traj_args* args, float* q_out, void* stream);
 int isdf_traj_step(const isdf_traj_args* args, const float* sdf, const float* grad, double* records, float* q_out, double* grad_out,
                    void* stream);
 
+/* ---- planning for articulated robots: trajectory steps in joint space ------------------
+ * isdf_traj_step for a robot that has joints: a serial kinematic chain with collision spheres on its links -- an arm, a free-
+ * flying rigid body (three prismatic and three revolute joints), a mobile base with yaw.  The caller evaluates its field at the
+ * query points, one launch turns the values into the cost, its exact gradient pulled back through the chain's Jacobian, the
+ * preconditioned and projected step, and the query points of the next iteration.  Reference: none.
+ *
+ * The chain (HOST arrays, read and checked before the call returns; they travel as launch arguments): J joints, joint j = 1 .. J
+ * of kind 0 (revolute) or 1 (prismatic), with a fixed transform X_j (3x4 row-major, [R | t]) from the previous link's frame and a
+ * unit axis u_j in its own frame; base (3x4) is the world pose of link 0.  S spheres: sphere s sits on link l_s in [0, J] at the
+ * local centre o_s with radius r_s.  A sphere on link 0 does not move: it counts in the cost and pulls on no joint.  Optional
+ * limits lo_j <= hi_j (fp32, +-inf: none; a NULL array: none for every joint).  Branches and closed loops are not described.
+ *
+ * B trajectories of T configurations theta[b][t][j] (fp32); rows 0 and T-1 are fixed, 1 .. T-2 are INTERIOR.
+ *
+ * Everything in double on the fp32 inputs widened, every operation rounded on its own, no fused multiply-add, products and
+ * sums in the order written; dot(a, b) = (a0 b0 + a1 b1) + a2 b2, a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).
+ * Frames of one configuration (R: 3x3, rows R_0 R_1 R_2; t: 3), link by link:
+ *   (R, t) = base.  For j = 1 .. J:  A = R X_j.R with A[r][c] = dot(R_r, column c of X_j.R);  p_j[r] = dot(R_r, X_j.t) + t[r];
+ *     a_j[r] = dot(A_r, u_j)   (the joint's world axis; p_j is its world origin)
+ *     revolute:  s = sin(theta_j), c = cos(theta_j), k = 1 - c,
+ *       M = [ c + k (u0 u0)       k (u0 u1) - s u2    k (u0 u2) + s u1 ]
+ *           [ k (u1 u0) + s u2    c + k (u1 u1)       k (u1 u2) - s u0 ]
+ *           [ k (u2 u0) - s u1    k (u2 u1) + s u0    c + k (u2 u2)    ],  R <- A M with R[r][c] = dot(A_r, column c of M), t <- p_j
+ *     prismatic: R <- A, t[r] <- p_j[r] + theta_j * a_j[r]
+ *   Query points, layout [B][T][S][3]: q[s][r] = (float)(dot(R_r, o_s) + t[r]) under the frame of link l_s.
+ *
+ * The step, from q (the fp32 query points the field was evaluated at), sdf and grad:
+ *   sample (t, s), every t, s ascending: BAD iff sdf or one of the three grad values is not finite; a bad sample adds its number
+ *     of non-finite values to [8] and nothing else (its c, c' and r are 0).  Otherwise d = sdf - r_s and c, c' as for
+ *     isdf_traj_step; c = c' = 0 at t = 0 and t = T-1.
+ *   body-point velocity, interior t: v = (q_{t+1,s} - q_{t-1,s}) * 0.5, sigma = sqrt((v0 v0 + v1 v1) + v2 v2), h = v / sigma (0
+ *     where sigma == 0; h = 0 at t = 0 and t = T-1)
+ *   F_obs = sum_{t=1}^{T-2} (sum_s c_{t,s} * sigma_{t,s})      F_smooth = (0.5 * (T-1)) * sum_{t=0}^{T-2} sum_j (theta_{t+1,j} - theta_{t,j})^2
+ *   workspace force, interior t, sample not bad: r = (sigma * c') * g + (c_{t-1,s} * h_{t-1,s} - c_{t+1,s} * h_{t+1,s}) * 0.5
+ *   per link l = 1 .. J, s ascending over the spheres with l_s = l, from 0:  R_l = sum r,  M_l = sum q_{t,s} x r
+ *   suffix sums over the links, j = J-1 down to 1:  Rs_J = R_J, Rs_j = Rs_{j+1} + R_j;  Ms_J = M_J, Ms_j = Ms_{j+1} + M_j
+ *   revolute:  o_j = dot(a_j, Ms_j - p_j x Rs_j)       prismatic:  o_j = dot(a_j, Rs_j)       (a_j, p_j at waypoint t)
+ *   grad_t[j] = w_obs * o_j + (w_smooth * (T-1)) * ((2 theta_{t,j} - theta_{t-1,j}) - theta_{t+1,j}); rows 0 and T-1 are 0.  This
+ *     is the exact gradient of w_obs F_obs + w_smooth F_smooth in theta_t with q, sigma and h as functions of theta.
+ *   step: y = K^-1 grad per joint exactly as for isdf_traj_step (the same two ordered prefix sums), Delta = -(y / (eta * (T-1))),
+ *     z0 = theta + Delta, z = min(max(z0, lo_j), hi_j), Delta' = z - theta; the entry is CUT iff z != z0
+ *     m = max_{t,j} |Delta'| (the infinity norm: radians and metres are not mixed into a 2-norm);
+ *     kappa = 1 if m <= max_step, else max_step / m;  theta <- (float)((double)theta + kappa * Delta')
+ *     A theta inside [lo, hi] stays inside; one outside is moved towards the interval.
+ * State and its rules: those of isdf_traj_step.  Record, ISDF_TRAJ_RECORD doubles per trajectory: [0] .. [9] as for
+ * isdf_traj_step with the definitions above, [10] the joint-space path length sum_t sqrt(sum_j (theta_{t+1,j} - theta_{t,j})^2)
+ * (j ascending), [11] the number of cut entries (0, as [6], for a trajectory that did not enter as moving), [12..15] 0.  [5] =
+ * sum_t (sum_j grad_t[j]^2), j ascending.  Sums over t: thread k of 256 takes waypoints k, k + 256, .. in ascending order, lanes
+ * by shuffle, the four waves in wave order.  A trajectory's record and its new theta repeat bit for bit from run to run and do not
+ * depend on which other trajectories share the call.  theta must be finite (device data, not checked).
+ *
+ * ISDF_ARM_MAX_WAYPOINTS: the step keeps 2 J doubles per waypoint in LDS (the gradient that becomes the step, and the prefix
+ * sums), 16 J T bytes: 48 KB at 8 joints and 384 waypoints, which fits the 64 KB a workgroup gets without an opt-in.
+ * ISDF_ARM_MAX_TRAJ: the smallest power of two at which B * T * S can pass 2^31 - 1 at all.
+ *
+ * Every call: ISDF_EINVAL for a NULL args / theta / base / X / kinds / axes / links / centres / radii / output / input (lo and
+ * hi may be NULL; state may be NULL for isdf_arm_points only), B outside [1, ISDF_ARM_MAX_TRAJ], T outside [3,
+ * ISDF_ARM_MAX_WAYPOINTS], J outside [1, ISDF_ARM_MAX_JOINTS], S outside [1, ISDF_ARM_MAX_SPHERES], B * T * S > 2^31 - 1, a
+ * kind outside {0, 1}, a link outside [0, J], an axis whose fp32 (u0 u0 + u1 u1) + u2 u2 is further than 1e-5 from 1, an entry
+ * of X, base or the centres that is not finite, a radius that is negative or not finite, lo_j > hi_j or a NaN limit; the step
+ * also for the parameters isdf_traj_step refuses.  Nothing is launched by a refused call.                                  */
+#define ISDF_ARM_MAX_JOINTS 8
+#define ISDF_ARM_MAX_SPHERES 64
+#define ISDF_ARM_MAX_WAYPOINTS 384
+#define ISDF_ARM_MAX_TRAJ 131072
+
+typedef struct isdf_arm_args {
+  int32_t B, T, J, S;
+  float eps, w_obs, w_smooth, eta, max_step, tol;
+  float* theta;            /* device [B][T][J]; isdf_arm_step updates it in place */
+  int32_t* state;          /* device [B]; may be NULL for isdf_arm_points          */
+  const float* base;       /* HOST [12]    */
+  const float* X;          /* HOST [J][12] */
+  const int32_t* kinds;    /* HOST [J]     */
+  const float* axes;       /* HOST [J][3]  */
+  const int32_t* links;    /* HOST [S]     */
+  const float* centres;    /* HOST [S][3]  */
+  const float* radii;      /* HOST [S]     */
+  const float* lo;         /* HOST [J], or NULL */
+  const float* hi;         /* HOST [J], or NULL */
+} isdf_arm_args;
+
+/* q_out [B][T][S][3] <- the query points of theta.  One launch. */
+int isdf_arm_points(const isdf_arm_args* args, float* q_out, void* stream);
+
+/* One iteration from q [B][T][S][3], sdf [B][T][S] and grad [B][T][S][3] (device fp32; q: the points the field was evaluated
+ * at): records [B][ISDF_TRAJ_RECORD] (device doubles), grad_out [B][T][J] (device doubles, or NULL) <- grad, theta and state
+ * updated in place, q_out (or NULL; it may be q itself) <- the query points of the theta the call leaves, for every trajectory,
+ * frozen ones included.  One launch, one workgroup per trajectory. */
+int isdf_arm_step(const isdf_arm_args* args, const float* q, const float* sdf, const float* grad, double* records, float* q_out,
+                  double* grad_out, void* stream);
+
 /* ---- the voxel baseline: TSDF fusion and the exact Euclidean distance transform ------------
  * What the map is compared with (eval/plot_utils.py:108-130 reads a "GPU fusion" result; the reference does not ship the fusion):
  * the posed depth frames fused into a truncated signed distance volume, and the full-range field of an occupancy grid by two

@@ -106,6 +106,15 @@ class TrajArgs(C.Structure):
                 ("x", C.c_void_p), ("state", C.c_void_p), ("offsets", C.c_void_p), ("radii", C.c_void_p)]
 
 
+class ArmArgs(C.Structure):
+    """isdf_arm_args (everything from base on is a HOST array)"""
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("J", C.c_int32), ("S", C.c_int32), ("eps", C.c_float),
+                ("w_obs", C.c_float), ("w_smooth", C.c_float), ("eta", C.c_float), ("max_step", C.c_float), ("tol", C.c_float),
+                ("theta", C.c_void_p), ("state", C.c_void_p), ("base", C.c_void_p), ("X", C.c_void_p), ("kinds", C.c_void_p),
+                ("axes", C.c_void_p), ("links", C.c_void_p), ("centres", C.c_void_p), ("radii", C.c_void_p), ("lo", C.c_void_p),
+                ("hi", C.c_void_p)]
+
+
 class TsdfArgs(C.Structure):
     """isdf_tsdf_args"""
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
@@ -149,7 +158,8 @@ POSE_RECORD = 32                                      # ISDF_POSE_RECORD (double
 POSE_MAX_BLOCKS = 64                                  # ISDF_POSE_MAX_BLOCKS
 TRAJ_RECORD = 16                                      # ISDF_TRAJ_RECORD (doubles per trajectory)
 TRAJ_MAX_WAYPOINTS, TRAJ_MAX_SPHERES, TRAJ_MAX_TRAJ = 1024, 32, 65536    # ISDF_TRAJ_MAX_*
-EDT_NONE, EDT_MAX_SIDE = 1 << 30, 1024                # ISDF_EDT_NONE, ISDF_EDT_MAX_SIDE
+ARM_MAX_JOINTS, ARM_MAX_SPHERES, ARM_MAX_WAYPOINTS, ARM_MAX_TRAJ = 8, 64, 384, 131072    # ISDF_ARM_MAX_*
+EDT_NONE, EDT_MAX_SIDE = 1 << 30, 1024              # ISDF_EDT_NONE, ISDF_EDT_MAX_SIDE
 TRI_TILE, TRI_SLOT_FLOATS, TRI_RECORD = 256, 24, 4   # ISDF_TRI_TILE, ISDF_TRI_SLOT_FLOATS, ISDF_TRI_RECORD (doubles)
 ROUTE_NONE, ROUTE_MAX_VOXELS, ROUTE_TILE = 1 << 30, 1 << 27, 8    # ISDF_ROUTE_NONE, ISDF_ROUTE_MAX_VOXELS, ISDF_ROUTE_TILE
 FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
@@ -172,7 +182,7 @@ STRUCTS = {"isdf_net_cfg": NetCfg, "isdf_sample_args": SampleArgs, "isdf_sample_
            "isdf_step_args": StepArgs, "isdf_step_out": StepOut, "isdf_optim_args": OptimArgs, "isdf_mc_args": McArgs,
            "isdf_render_args": RenderArgs, "isdf_gt_volume": GtVolumeArgs, "isdf_region_args": RegionArgs,
            "isdf_colormap": ColormapArgs, "isdf_band_args": BandArgs, "isdf_pose_args": PoseArgs, "isdf_traj_args": TrajArgs,
-           "isdf_tsdf_args": TsdfArgs}
+           "isdf_arm_args": ArmArgs, "isdf_tsdf_args": TsdfArgs}
 
 # every function include/isdf_hip.h declares, in header order: name -> (restype, argtypes).  This is the one place a function is
 # declared on the Python side; tests/test_abi.py holds every line (and STRUCTS, and the constants above) to the header.
@@ -221,6 +231,8 @@ PROTOTYPES = {
     "isdf_pose_system": (C.c_int, [P(PoseArgs), vp, vp, vp, f32, f32, vp, vp, i64, vp]),
     "isdf_traj_points": (C.c_int, [P(TrajArgs), vp, vp]),
     "isdf_traj_step": (C.c_int, [P(TrajArgs), vp, vp, vp, vp, vp, vp]),
+    "isdf_arm_points": (C.c_int, [P(ArmArgs), vp, vp]),
+    "isdf_arm_step": (C.c_int, [P(ArmArgs), vp, vp, vp, vp, vp, vp, vp]),
     "isdf_tsdf_integrate": (C.c_int, [P(TsdfArgs), vp]),
     "isdf_edt_ws_bytes": (i64, [i32, i32, i32]),
     "isdf_distance_transform": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i64, vp]),

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
-SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "fusion.hip", "tri.hip", "route.hip", "capi.hip"]
+SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "arm.hip", "fusion.hip", "tri.hip", "route.hip", "capi.hip"]
 HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "block_reduce.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
@@ -41,6 +41,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 # model bit for bit (every operation rounded, no fused multiply-add), and its double sums are stated product by product.
 # traj.hip: three coordinates through the same chain once more; its query points must equal an fp32 model bit for bit and its
 # double terms a float64 model written in the same order.
+# arm.hip: traj.hip's flags for traj.hip's reasons: rows of a frame against one vector, and double terms that a float64 model written
+# in the same order must repeat.  Its chain description (1.9 KB of launch arguments) is read in loops unrolled over joints: more
+# uses than the 300 up to which the compiler reads a by-value argument where it lies; past that it copies the struct to scratch.
 # fusion.hip: eight frames' camera transforms of one voxel side by side, visible.hip's shape and the refused form again; the fused
 # (tsdf, weight) pair must equal an fp32 model bit for bit (every operation rounded, no fused multiply-add).
 # tri.hip: four query points against one triangle, the triangle the shared operand of the same refused form; closest point, squared
@@ -52,7 +55,8 @@ PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-thr
             "reduce.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "slices.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "visible.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "band.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "pose.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
-            "traj.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "fusion.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
+            "traj.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "arm.hip": ["-fno-slp-vectorize", "-ffp-contract=off", "-mllvm", "-instcombine-max-copied-from-constant-users=100000"],
+            "fusion.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "tri.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
 
 

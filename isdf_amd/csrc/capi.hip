@@ -680,6 +680,52 @@ int isdf_traj_step(const isdf_traj_args* a, const float* sdf, const float* grad,
   return launch_traj_step(*a, sdf, grad, records, q_out, grad_out, (hipStream_t)stream);
 }
 
+// ---- planning for articulated robots (arm.hip)
+// everything of isdf_arm_args the host can check: the sizes and the chain entry by entry
+static bool arm_args_ok(const isdf_arm_args* a) {
+  if (!a || !a->theta || !a->base || !a->X || !a->kinds || !a->axes || !a->links || !a->centres || !a->radii) return false;
+  if (a->B < 1 || a->B > ISDF_ARM_MAX_TRAJ || a->T < 3 || a->T > ISDF_ARM_MAX_WAYPOINTS || a->J < 1 || a->J > ISDF_ARM_MAX_JOINTS ||
+      a->S < 1 || a->S > ISDF_ARM_MAX_SPHERES)
+    return false;
+  if ((int64_t)a->B * a->T * a->S > 0x7fffffff) return false;
+  for (int i = 0; i < 12; ++i)
+    if (!__builtin_isfinite(a->base[i])) return false;
+  for (int32_t i = 0; i < a->J * 12; ++i)
+    if (!__builtin_isfinite(a->X[i])) return false;
+  for (int32_t j = 0; j < a->J; ++j) {
+    if (a->kinds[j] != 0 && a->kinds[j] != 1) return false;
+    const float* u = a->axes + j * 3;
+    const float n2 = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+    if (!(__builtin_fabsf(n2 - 1.f) <= 1e-5f)) return false;                                              // also refuses NaN
+    const float lo = a->lo ? a->lo[j] : -__builtin_inff(), hi = a->hi ? a->hi[j] : __builtin_inff();
+    if (!(lo <= hi)) return false;                                                                        // also refuses NaN
+  }
+  for (int32_t s = 0; s < a->S; ++s) {
+    if (a->links[s] < 0 || a->links[s] > a->J) return false;
+    for (int k = 0; k < 3; ++k)
+      if (!__builtin_isfinite(a->centres[s * 3 + k])) return false;
+    if (!(a->radii[s] >= 0.f) || !__builtin_isfinite(a->radii[s])) return false;
+  }
+  return true;
+}
+
+int isdf_arm_points(const isdf_arm_args* a, float* q_out, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!arm_args_ok(a) || !q_out) return ISDF_EINVAL;
+  return launch_arm_points(*a, q_out, (hipStream_t)stream);
+}
+
+int isdf_arm_step(const isdf_arm_args* a, const float* q, const float* sdf, const float* grad, double* records, float* q_out,
+                  double* grad_out, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!arm_args_ok(a) || !a->state || !q || !sdf || !grad || !records) return ISDF_EINVAL;
+  if (!(a->eps > 0.f) || !(a->eta > 0.f) || !(a->max_step > 0.f)) return ISDF_EINVAL;                  // also refuses NaN
+  if (!__builtin_isfinite(a->eps) || !__builtin_isfinite(a->eta)) return ISDF_EINVAL;                   // max_step may be +inf
+  for (float v : {a->w_obs, a->w_smooth, a->tol})
+    if (!(v >= 0.f) || !__builtin_isfinite(v)) return ISDF_EINVAL;
+  return launch_arm_step(*a, q, sdf, grad, records, q_out, grad_out, (hipStream_t)stream);
+}
+
 // ---- the voxel baseline: TSDF fusion and the distance transform (fusion.hip)
 int isdf_tsdf_integrate(const isdf_tsdf_args* a, void* stream) {
   isdf_clear_stale_hip_error();

@@ -64,6 +64,9 @@ int launch_pose_system(const isdf_pose_args& a, const float* pts, const float* s
 int launch_traj_points(const isdf_traj_args& a, float* q_out, hipStream_t st);                                       // traj.hip
 int launch_traj_step(const isdf_traj_args& a, const float* sdf, const float* grad, double* records, float* q_out, double* grad_out,
                      hipStream_t st);
+int launch_arm_points(const isdf_arm_args& a, float* q_out, hipStream_t st);                                         // arm.hip
+int launch_arm_step(const isdf_arm_args& a, const float* q, const float* sdf, const float* grad, double* records, float* q_out,
+                    double* grad_out, hipStream_t st);
 int launch_tsdf_integrate(const isdf_tsdf_args& a, hipStream_t st);                                                 // fusion.hip
 int64_t edt_volume_bytes(int32_t nx, int32_t ny, int32_t nz);
 int launch_distance_transform(const uint8_t* feature, int32_t nx, int32_t ny, int32_t nz, int invert, int32_t* dist2, int32_t* scratch,

@@ -1131,6 +1131,78 @@ class Engine:
                                            _ffi.ptr(q_out), _ffi.ptr(gout), _stream(self.device)), "isdf_traj_step")
         return (out, gout) if want_grad else out
 
+    # ---- planning for articulated robots -----------------------------------------------
+    def _arm_args(self, name, theta, chain):
+        """(isdf_arm_args, what it points to, B, T, J, S): theta [B,T,J] f32 on the device, used where it lies (the step writes
+        it); chain: anything with the attributes of isdf_amd.kinematics.Chain (base [3,4], X [J,3,4], kinds [J], axes [J,3],
+        links [S], centres [S,3], radii [S], lo / hi [J] or None), read as HOST arrays, checked by the call and handed on as launch
+        arguments"""
+        if not torch.is_tensor(theta) or theta.dim() != 3 or theta.dtype != torch.float32 or not theta.is_contiguous():
+            raise ValueError("%s: theta must be a contiguous float32 tensor [B, T, J]" % name)
+        self._check_device(name, "theta", theta)
+        B, T, J = (int(v) for v in theta.shape)
+        f, i = np.float32, np.int32
+        keep = dict(base=np.ascontiguousarray(host_array(chain.base, f)).reshape(-1), X=np.ascontiguousarray(host_array(chain.X, f)).reshape(-1),
+                    kinds=np.ascontiguousarray(host_array(chain.kinds, i)).reshape(-1), axes=np.ascontiguousarray(host_array(chain.axes, f)).reshape(-1),
+                    links=np.ascontiguousarray(host_array(chain.links, i)).reshape(-1), centres=np.ascontiguousarray(host_array(chain.centres, f)).reshape(-1),
+                    radii=np.ascontiguousarray(host_array(chain.radii, f)).reshape(-1))
+        for k in ("lo", "hi"):
+            v = getattr(chain, k, None)
+            if v is not None:
+                keep[k] = np.ascontiguousarray(host_array(v, f)).reshape(-1)
+        S = int(keep["links"].size)
+        want = dict(base=12, X=12 * J, kinds=J, axes=3 * J, links=S, centres=3 * S, radii=S, lo=J, hi=J)
+        for k, v in keep.items():
+            if v.size != want[k] or v.size == 0:
+                raise ValueError("%s: the chain's %s has %d entries; theta's %d joints and %d spheres need %d" % (name, k, v.size, J, S, want[k]))
+        a = _ffi.ArmArgs()
+        a.B, a.T, a.J, a.S = B, T, J, S
+        a.theta = _addr(theta)
+        for k, v in keep.items():
+            setattr(a, k, v.ctypes.data)
+        return a, keep, B, T, J, S
+
+    def arm_points(self, theta, chain):
+        """q [B*T*S, 3] f32 on the device: isdf_arm_points, the world centres of the chain's S collision spheres at every
+        configuration theta[b][t] (forward kinematics in double, rounded once to fp32; layout [B][T][S]).  theta: contiguous
+        float32 [B,T,J] on the device; chain: isdf_amd.kinematics.Chain.  No host synchronisation."""
+        a, keep, B, T, J, S = self._arm_args("arm_points", theta, chain)
+        q = torch.empty(B * T * S, 3, dtype=torch.float32, device=self.device)
+        _ffi.check(self.lib.isdf_arm_points(C.byref(a), _addr(q), _stream(self.device)), "isdf_arm_points")
+        return q
+
+    def arm_step(self, theta, state, chain, q, sdf, grad, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=32.0, max_step=0.05, tol=1e-5,
+                 out=None, q_out=None, want_grad=False):
+        """records f64 [B, 16] on the device (and the cost gradient f64 [B,T,J] with want_grad): isdf_arm_step, one iteration of
+        covariant gradient descent on B joint-space trajectories from the field values sdf [B*T*S] and gradients grad [B*T*S,3]
+        (device f32) at the query points q [B*T*S,3] = `arm_points(theta, chain)`.  theta (contiguous float32 [B,T,J]) and state
+        (contiguous int32 [B]: 0 moving, 1 converged, 2 invalid) are MODIFIED IN PLACE: a moving trajectory takes the step
+        -(1/eta) K^-1 grad, projected onto the joint limits and scaled so that no joint moves further than max_step, unless a field
+        value is not finite (-> 2) or the step is below tol (-> 1); the others are left bit for bit.  Record: [0] .. [9] as
+        `traj_step`, [10] the joint-space path length, [11] the entries of the step a limit cut (include/isdf_hip.h).  out: a
+        contiguous float64 [B, 16] to write into; q_out: a contiguous float32 tensor of B*T*S*3 values (it may be q) that
+        receives the query points of the theta the call leaves -- the next field call's input.  One launch, summed in a fixed
+        order: the same inputs give the same bytes, whatever else shares the call.  No host synchronisation."""
+        a, keep, B, T, J, S = self._arm_args("arm_step", theta, chain)
+        if not torch.is_tensor(state) or state.dtype != torch.int32 or state.numel() != B or not state.is_contiguous() \
+                or state.device != theta.device:
+            raise ValueError("arm_step: state must be a contiguous int32 tensor [%d] on theta's device" % B)
+        p, s, g = self._flat(q, torch.float32, 3), self._flat(sdf, torch.float32), self._flat(grad, torch.float32, 3)
+        n = B * T * S
+        if not (int(p.shape[0]) == s.numel() == int(g.shape[0]) == n):
+            raise ValueError("arm_step: %d x %d x %d needs %d points, sdf values and gradients (got %d, %d, %d)"
+                             % (B, T, S, n, p.shape[0], s.numel(), g.shape[0]))
+        out = self._record_out("arm_step", out, B, _ffi.TRAJ_RECORD, on=theta.device)
+        if q_out is not None and (q_out.dtype != torch.float32 or q_out.numel() != n * 3 or not q_out.is_contiguous()
+                                  or q_out.device != theta.device):
+            raise ValueError("arm_step: q_out must be a contiguous float32 tensor of %d x 3 values on theta's device" % n)
+        gout = torch.empty(B, T, J, dtype=torch.float64, device=self.device) if want_grad else None
+        a.state = _addr(state)
+        a.eps, a.w_obs, a.w_smooth, a.eta, a.max_step, a.tol = (float(v) for v in (eps, w_obs, w_smooth, eta, max_step, tol))
+        _ffi.check(self.lib.isdf_arm_step(C.byref(a), _addr(p), _addr(s), _addr(g), _ffi.ptr(out), _ffi.ptr(q_out), _ffi.ptr(gout),
+                                          _stream(self.device)), "isdf_arm_step")
+        return (out, gout) if want_grad else out
+
     # ---- SDF slice images --------------------------------------------------------------
     def slice_images(self, pts, sdf, cmap=None, volume=None, chomp_eps=None, oob_fill=0.0):
         """(pred_rgb u8 [n,3], gt f32 [n], gt_rgb u8 [n,3], pred_cost f32 [n], gt_cost f32 [n]) on the device, None for what was
