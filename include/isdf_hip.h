@@ -1064,6 +1064,73 @@ int64_t isdf_tri_ws_bytes(int64_t n, int64_t m);
 int isdf_tri_distance(const float* pts, int64_t n, const float* packed, int64_t m, float* dist, int32_t* index, float* closest,
                       float* winding, double* record, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the same distance at scan scale: a flat tile index, conservative culling, far-field winding number ---------------------
+ * isdf_tri_distance visits every pair.  isdf_tri_distance_tiles visits the tiles of ISDF_TRI_TILE triangles that can still hold
+ * the nearest one, and returns THE SAME BITS in dist, index, closest and record: the winner is the integer minimum of
+ * (dist2's bits << 32 | index), which no visiting order changes, and a tile is left out only when none of its triangles can
+ * reach that minimum (the rule and its margin below).  The winding number is a sum over all faces and cannot be culled exactly:
+ * a tile far from the query block adds one dipole term instead of its triangles' solid angles, an approximation the caller opts
+ * into by beta > 0 and whose error depends on beta and on the order.
+ *
+ * order: device int32 [n_order], n_order a multiple of ISDF_TRI_TILE: slot indices into `packed`, or -1 for nothing; tile t lists
+ * entries [t * ISDF_TRI_TILE, (t + 1) * ISDF_TRI_TILE).  The order is the caller's (a space-filling curve over the centroids, with the
+ * few very large faces in tiles of their own, keeps the boxes small); no result of the distance depends on it.  Every valid slot
+ * should be listed exactly once: a slot that is not listed is never found, one listed twice counts twice in the winding number.
+ *
+ * isdf_tri_tiles_build, one workgroup per tile: every entry is tested against [0, S) or -1 before anything is read through it
+ * (S as for isdf_tri_pack); order_clean [n_order] receives the entry if it names a VALID slot and -1 otherwise; counts (device
+ * int32[2], zeroed by the call): [0] entries that are neither -1 nor inside [0, S), [1] valid slots listed.  tiles: device double
+ * [n_order / ISDF_TRI_TILE][ISDF_TRI_TILE_RECORD], over the vertices a, b, c of the tile's valid slots as double:
+ *   [0..2] box lo   [3..5] box hi   (the exact float values; +inf / -inf for an empty tile)
+ *   [6..8] N = sum of (1/2) (b - a) x (c - a)      [9..11] c = sum of area * ((a + b) + c) / 3, over sum of area    [12] r = max |vertex - c|
+ *   [13] sum of area, area = (1/2) |(b - a) x (c - a)|     [14] the number of valid slots     [15] extent: one past the tile's last valid entry
+ * the sums in the record kernels' one order (lanes by shuffle halving, the four waves in wave order).  A tile with [14] = 0 is
+ * empty and never visited.  One launch.  ISDF_EINVAL: a NULL counts, m < 0 or > 2^30, n_order < 0, > 2^31 - ISDF_TRI_TILE or no
+ * multiple of ISDF_TRI_TILE, a NULL order / tiles / order_clean with n_order > 0, a NULL packed with m > 0.
+ *
+ * isdf_tri_distance_tiles.  qperm: device int32 [n], a permutation of the queries that makes runs of 1024 spatially compact; block
+ * g takes entries [1024 g, 1024 g + 1024).  An entry outside [0, n) is skipped and counted, before anything is read or written
+ * through it; a query that no entry names gets dist = +inf, index = -1, winding = 0.  THE RULE, per block, in double:
+ *   [bl, bh] = the box of the block's finite query points (a block without one visits nothing)
+ *   per non-empty tile t with box [tl, th]:   mind = sqrt((gx*gx + gy*gy) + gz*gz),  g_k = max(0, tl_k - bh_k, bl_k - th_k)
+ *                                             maxd = sqrt((hx*hx + hy*hy) + hz*hz),  h_k = max(|th_k - bl_k|, |bh_k - tl_k|)
+ *   seed = the lowest t with the least maxd: visited first, and staged for the distance
+ *   U = the largest running best dist2 (fp32) over the block's finite queries, recomputed after every tile staged for the distance
+ *   the other tiles in ascending order: t is staged for the distance iff   mind - ISDF_TRI_TILE_EPS * maxd <= sqrt((double)U)
+ * Every triangle of a tile left out is farther than sqrt(U) + EPS * maxd from every query of the block, and the per-pair sequence
+ * errs by less than EPS * |p - a| <= EPS * maxd in the distance (fl(p - a) is exact to half an ulp per component, the dot products
+ * and the residual add a few ulp of |p - a| each: under 16 * 2^-24 in all, EPS = 2^-16 leaves a factor 16), so its computed dist2
+ * exceeds U and cannot win or tie.  A sliver whose normal or weights lose all their digits is outside this bound, as it is outside
+ * the documented accuracy of isdf_tri_distance itself.
+ * A staged tile is gathered through order_clean (entries tested against [0, S) once more) and passes through the per-pair
+ * sequence of isdf_tri_distance, the slot index as the face index.
+ * Winding number (winding != NULL): with e_k = max(0, c_k - bh_k, bl_k - c_k), tile t is FAR iff beta > 0 and
+ *   sqrt((ex*ex + ey*ey) + ez*ez) >= beta * r        (the whole block decides alike)
+ * a far tile adds, per query q in double with d = c - q and r2 = (dx*dx + dy*dy) + dz*dz,   ((Nx*dx + Ny*dy) + Nz*dz) / (r2 * sqrt(r2));
+ * a near tile is staged and adds the fp32 solid angles of its valid slots as isdf_tri_distance computes them, in entry order.  The
+ * terms are added to the query's double in visiting order (the seed, then ascending): bits repeat from run to run.  beta <= 0:
+ * every tile is near, and the sum is isdf_tri_distance's up to the order of summation.  A tile may be staged for the distance, for
+ * the winding number, or for both.
+ * stats: device int64[4] or NULL, zeroed by the call: [0] tiles staged for the distance, summed over blocks  [1] tiles staged as
+ * near  [2] blocks  [3] qperm entries skipped.
+ * dist, index, closest, winding may be NULL; record as for isdf_tri_distance, required.  Up to three asynchronous memsets and three
+ * launches.  ISDF_EINVAL: a NULL record, n or m < 0 or > 2^30, n_tiles < 0 or > 2^23, a NULL pts or qperm with n > 0, a NULL tiles
+ * or order_clean with n_tiles > 0, a NULL packed with m > 0, a beta that is NaN.  ISDF_EWORKSPACE: a workspace that is NULL or
+ * smaller than isdf_tri_tiles_ws_bytes(n). */
+#define ISDF_TRI_TILE_RECORD 16
+#define ISDF_TRI_TILE_EPS (1.0 / 65536.0)
+
+int isdf_tri_tiles_build(const float* packed, int64_t m, const int32_t* order, int64_t n_order, double* tiles, int32_t* order_clean,
+                         int32_t* counts, void* stream);
+
+/* 16*n + 32*ceil(n / 256) + 256: one 64-bit key and one double per point, one partial record per 256 points.  ISDF_EINVAL for
+ * n < 0 or > 2^30. */
+int64_t isdf_tri_tiles_ws_bytes(int64_t n);
+
+int isdf_tri_distance_tiles(const float* pts, int64_t n, const int32_t* qperm, const float* packed, int64_t m, const double* tiles,
+                            const int32_t* order_clean, int64_t n_tiles, double beta, float* dist, int32_t* index, float* closest,
+                            float* winding, double* record, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- routing through the map: geodesic distance field of a free-space mask and the path down it --------------------------
  * The global half of planning (the local half is isdf_traj_step, which deforms a seed and cannot change which side of an obstacle
  * it passes): shortest routes over the free voxels of a grid.  The reference has no counterpart.  Volumes are [nx][ny][nz],

@@ -161,6 +161,7 @@ TRAJ_MAX_WAYPOINTS, TRAJ_MAX_SPHERES, TRAJ_MAX_TRAJ = 1024, 32, 65536    # ISDF_
 ARM_MAX_JOINTS, ARM_MAX_SPHERES, ARM_MAX_WAYPOINTS, ARM_MAX_TRAJ = 8, 64, 384, 131072    # ISDF_ARM_MAX_*
 EDT_NONE, EDT_MAX_SIDE = 1 << 30, 1024              # ISDF_EDT_NONE, ISDF_EDT_MAX_SIDE
 TRI_TILE, TRI_SLOT_FLOATS, TRI_RECORD = 256, 24, 4   # ISDF_TRI_TILE, ISDF_TRI_SLOT_FLOATS, ISDF_TRI_RECORD (doubles)
+TRI_TILE_RECORD = 16                                  # ISDF_TRI_TILE_RECORD (doubles per tile)
 ROUTE_NONE, ROUTE_MAX_VOXELS, ROUTE_TILE = 1 << 30, 1 << 27, 8    # ISDF_ROUTE_NONE, ISDF_ROUTE_MAX_VOXELS, ISDF_ROUTE_TILE
 FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
 
@@ -240,6 +241,9 @@ PROTOTYPES = {
     "isdf_tri_pack": (C.c_int, [vp, i64, vp, i64, P(f32), vp, i64, vp, vp]),
     "isdf_tri_ws_bytes": (i64, [i64, i64]),
     "isdf_tri_distance": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "isdf_tri_tiles_build": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp]),
+    "isdf_tri_tiles_ws_bytes": (i64, [i64]),
+    "isdf_tri_distance_tiles": (C.c_int, [vp, i64, vp, vp, i64, vp, vp, i64, C.c_double, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "isdf_route_init": (C.c_int, [vp, i32, i32, i32, vp, i32, vp, vp]),
     "isdf_route_ws_bytes": (i64, [i32, i32, i32]),
     "isdf_route_relax": (C.c_int, [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp]),

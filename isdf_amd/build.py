@@ -11,8 +11,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
-SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "arm.hip", "fusion.hip", "tri.hip", "route.hip", "capi.hip"]
-HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "block_reduce.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
+SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "arm.hip", "fusion.hip", "tri.hip", "tri_tiles.hip", "route.hip", "capi.hip"]
+HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "block_reduce.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", "tri_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
 
@@ -48,6 +48,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 # (tsdf, weight) pair must equal an fp32 model bit for bit (every operation rounded, no fused multiply-add).
 # tri.hip: four query points against one triangle, the triangle the shared operand of the same refused form; closest point, squared
 # distance and index must equal an fp32 model bit for bit (every operation rounded, no fused multiply-add).
+# tri_tiles.hip: the same per-pair sequence (tri_dev.h) must give tri.hip's bits, so tri.hip's flags; its double rule and dipole
+# terms are restated by a float64 model operation for operation.
 # route.hip: int32 throughout, the default flags.
 PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"],
             "dw.hip": ["-fno-slp-vectorize"], "mesh.hip": ["-fno-slp-vectorize"],
@@ -57,7 +59,7 @@ PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-thr
             "band.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "pose.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "traj.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "arm.hip": ["-fno-slp-vectorize", "-ffp-contract=off", "-mllvm", "-instcombine-max-copied-from-constant-users=100000"],
             "fusion.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
-            "tri.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
+            "tri.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "tri_tiles.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
 
 
 def _hipcc():

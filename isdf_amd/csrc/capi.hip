@@ -794,6 +794,32 @@ int isdf_tri_distance(const float* pts, int64_t n, const float* packed, int64_t 
   return launch_tri_distance(pts, n, packed, m, dist, index, closest, winding, record, workspace, (hipStream_t)stream);
 }
 
+// ---- the tile index and the culled distance (tri_tiles.hip)
+int isdf_tri_tiles_build(const float* packed, int64_t m, const int32_t* order, int64_t n_order, double* tiles, int32_t* order_clean,
+                         int32_t* counts, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!counts || !tri_size_ok(m) || n_order < 0 || n_order > ((int64_t)1 << 31) - ISDF_TRI_TILE || n_order % ISDF_TRI_TILE != 0)
+    return ISDF_EINVAL;
+  if ((n_order > 0 && (!order || !tiles || !order_clean)) || (m > 0 && !packed)) return ISDF_EINVAL;
+  return launch_tri_tiles_build(packed, m, order, n_order, tiles, order_clean, counts, (hipStream_t)stream);
+}
+
+int64_t isdf_tri_tiles_ws_bytes(int64_t n) {
+  if (!tri_size_ok(n)) return ISDF_EINVAL;
+  return 16 * n + 32 * ((n + 255) / 256) + 256;
+}
+
+int isdf_tri_distance_tiles(const float* pts, int64_t n, const int32_t* qperm, const float* packed, int64_t m, const double* tiles,
+                            const int32_t* order_clean, int64_t n_tiles, double beta, float* dist, int32_t* index, float* closest,
+                            float* winding, double* record, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!record || !tri_size_ok(n) || !tri_size_ok(m) || n_tiles < 0 || n_tiles > ((int64_t)1 << 23) || beta != beta) return ISDF_EINVAL;
+  if ((n > 0 && (!pts || !qperm)) || (n_tiles > 0 && (!tiles || !order_clean)) || (m > 0 && !packed)) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_tri_tiles_ws_bytes(n)) return ISDF_EWORKSPACE;
+  return launch_tri_distance_tiles(pts, n, qperm, packed, m, tiles, order_clean, n_tiles, beta, dist, index, closest, winding, record,
+                                   stats, workspace, (hipStream_t)stream);
+}
+
 // ---- routing through the map (route.hip)
 static bool route_dims_ok(int32_t nx, int32_t ny, int32_t nz) {
   return nx >= 1 && ny >= 1 && nz >= 1 && (int64_t)nx * ny <= ISDF_ROUTE_MAX_VOXELS && (int64_t)nx * ny * nz <= ISDF_ROUTE_MAX_VOXELS;

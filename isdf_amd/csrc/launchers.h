@@ -77,6 +77,14 @@ int launch_tri_pack(const float* verts, int64_t nv, const int32_t* faces, int64_
                     hipStream_t st);
 int launch_tri_distance(const float* pts, int64_t n, const float* packed, int64_t m, float* dist, int32_t* index, float* closest,
                         float* winding, double* record, void* workspace, hipStream_t st);
+int launch_tri_finish(const float* pts, int64_t n, const float* packed, const unsigned long long* keys, const double* wpart,
+                      int64_t splits, float* dist, int32_t* index, float* closest, float* winding, double* record, double* part,
+                      hipStream_t st);
+int launch_tri_tiles_build(const float* packed, int64_t m, const int32_t* order, int64_t n_order, double* tiles, int32_t* order_clean,   // tri_tiles.hip
+                           int32_t* counts, hipStream_t st);
+int launch_tri_distance_tiles(const float* pts, int64_t n, const int32_t* qperm, const float* packed, int64_t m, const double* tiles,
+                              const int32_t* order_clean, int64_t n_tiles, double beta, float* dist, int32_t* index, float* closest,
+                              float* winding, double* record, int64_t* stats, void* workspace, hipStream_t st);
 int launch_route_init(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, const int32_t* goals, int32_t n_goals, int32_t* dist,   // route.hip
                       hipStream_t st);
 int64_t route_volume_bytes(int32_t nx, int32_t ny, int32_t nz);

@@ -207,6 +207,32 @@ def _addr(t):
     return t.data_ptr() if t is not None and t.numel() else None
 
 
+def morton_codes(p):
+    """int64 [n]: the 30-bit Morton code of every point of `p` [n,3] on a 1024^3 grid over the box of the finite points; 2^30 for a
+    point with a non-finite coordinate, so that a sort puts those last.  torch ops on p's device, no host synchronisation."""
+    p = p.reshape(-1, 3).to(torch.float32)
+    if p.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int64, device=p.device)
+    finite = torch.isfinite(p).all(1)
+    q = torch.where(finite[:, None], p, p.new_tensor(float("inf")))
+    lo = torch.where(finite.any(), q.amin(0), p.new_zeros(3))
+    q = torch.where(finite[:, None], p, lo[None, :])
+    ext = (q.amax(0) - lo).clamp_min(1e-30)
+    g = ((q - lo[None, :]) / ext[None, :] * 1023.0).clamp(0.0, 1023.0).to(torch.int64)
+    g = (g | (g << 16)) & 0x030000FF
+    g = (g | (g << 8)) & 0x0300F00F
+    g = (g | (g << 4)) & 0x030C30C3
+    g = (g | (g << 2)) & 0x09249249
+    code = g[:, 0] | (g[:, 1] << 1) | (g[:, 2] << 2)
+    return torch.where(finite, code, torch.full_like(code, 1 << 30))
+
+
+def morton_order(p):
+    """int32 [n]: the indices of the points of `p` [n,3] in Morton order (a stable sort of morton_codes), non-finite points last:
+    runs of consecutive entries are spatially compact.  No host synchronisation."""
+    return torch.sort(morton_codes(p), stable=True)[1].to(torch.int32)
+
+
 class Engine:
     def __init__(self, net: NetConfig, device="cuda"):
         self.lib = _ffi.lib()
@@ -1001,6 +1027,72 @@ class Engine:
                                               _addr(closest), _addr(winding), _ffi.ptr(record), _ffi.ptr(ws), int(ws.numel()),
                                               _stream(dev)), "isdf_tri_distance")
         return dist, index, closest, winding, record
+
+    def tri_tiles_build(self, packed, m, order):
+        """(tiles f64 [n_tiles, 16], order_clean i32 [n_order], counts i32 [2]) on the device: isdf_tri_tiles_build, the flat tile
+        index of a packed mesh for tri_distance_tiles.  order: integers [n_order], slot indices into `packed` or -1, padded here with
+        -1 to whole tiles; tile t lists entries 256 t .. 256 t + 255.  tiles: per tile the box, area vector, area-weighted centroid,
+        radius, area, count and extent of its valid slots (include/isdf_hip.h); order_clean: the entries that name a valid slot, -1
+        elsewhere; counts[0]: entries that are neither -1 nor a slot, counts[1]: valid slots listed.  No host synchronisation."""
+        m = int(m)
+        if packed.dtype != torch.float32 or not packed.is_contiguous() or packed.numel() * 4 < _ffi.tri_packed_bytes(m):
+            raise ValueError("tri_tiles_build: packed must be the contiguous float32 tensor tri_pack returned for %d faces" % m)
+        o = torch.as_tensor(order).detach().to(self.device)
+        if o.is_floating_point() or o.dtype == torch.bool:
+            raise ValueError("tri_tiles_build: order must be integers (got %s)" % o.dtype)
+        o = o.reshape(-1)
+        if o.dtype != torch.int32:                        # beyond int32: no slot either way; -2 is counted as a bad entry
+            o = torch.where((o < -1) | (o > 0x7fffffff), torch.full_like(o, -2), o).to(torch.int32)
+        pad = -int(o.numel()) % _ffi.TRI_TILE
+        if pad:
+            o = torch.cat([o, o.new_full((pad,), -1)])
+        o = o.contiguous()
+        n_order = int(o.numel())
+        tiles = torch.empty(n_order // _ffi.TRI_TILE, _ffi.TRI_TILE_RECORD, dtype=torch.float64, device=self.device)
+        clean = torch.empty(n_order, dtype=torch.int32, device=self.device)
+        counts = torch.empty(2, dtype=torch.int32, device=self.device)
+        _ffi.check(self.lib.isdf_tri_tiles_build(_addr(packed) if m else None, m, _addr(o), n_order, _addr(tiles), _addr(clean),
+                                                 _ffi.ptr(counts), _stream(self.device)), "isdf_tri_tiles_build")
+        return tiles, clean, counts
+
+    def tri_distance_tiles(self, packed, m, tiles, order_clean, pts, qperm=None, beta=0.0, want_index=False, want_closest=False,
+                           want_winding=False, want_dist=True, want_stats=False):
+        """(dist, index, closest, winding, record, stats) as tri_distance returns them, stats i64 [4] behind (None unless asked
+        for): isdf_tri_distance_tiles, the same distance, index, nearest point and record -- bit for bit -- from the tiles of the
+        index (tri_tiles_build) that a conservative test against each block of 1024 queries leaves.  winding: tiles farther than
+        beta radii from a block add their dipole term instead of their triangles (beta <= 0: none does).  qperm: int32 [n], the
+        order in which the queries form blocks; None: a Morton order of the points, non-finite points last (morton_order).
+        stats: tiles staged for the distance, tiles staged as near, blocks, qperm entries skipped.  No host synchronisation."""
+        p = self._flat(torch.as_tensor(pts), torch.float32, 3)
+        n, m, n_tiles = int(p.shape[0]), int(m), int(tiles.shape[0])
+        if packed.dtype != torch.float32 or not packed.is_contiguous() or packed.numel() * 4 < _ffi.tri_packed_bytes(m):
+            raise ValueError("tri_distance_tiles: packed must be the contiguous float32 tensor tri_pack returned for %d faces" % m)
+        if (tiles.dtype != torch.float64 or not tiles.is_contiguous() or tuple(tiles.shape) != (n_tiles, _ffi.TRI_TILE_RECORD)
+                or order_clean.dtype != torch.int32 or not order_clean.is_contiguous()
+                or order_clean.numel() != n_tiles * _ffi.TRI_TILE):
+            raise ValueError("tri_distance_tiles: tiles and order_clean must be the tensors tri_tiles_build returned")
+        for what, t in (("packed", packed), ("tiles", tiles), ("order_clean", order_clean)):
+            self._check_device("tri_distance_tiles", what, t)
+        if qperm is None:
+            qperm = morton_order(p)
+        qp = self._flat(torch.as_tensor(qperm), torch.int32)
+        if int(qp.numel()) != n:
+            raise ValueError("tri_distance_tiles: qperm must have one entry per point (got %d for %d)" % (qp.numel(), n))
+        need = int(self.lib.isdf_tri_tiles_ws_bytes(n))
+        _ffi.check(min(need, 0), "isdf_tri_tiles_ws_bytes(%d)" % n)
+        ws = self._scratch("tri_distance", need)
+        dev = self.device
+        dist = torch.empty(n, dtype=torch.float32, device=dev) if want_dist else None
+        index = torch.empty(n, dtype=torch.int32, device=dev) if want_index else None
+        closest = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_closest else None
+        winding = torch.empty(n, dtype=torch.float32, device=dev) if want_winding else None
+        stats = torch.empty(4, dtype=torch.int64, device=dev) if want_stats else None
+        record = torch.empty(_ffi.TRI_RECORD, dtype=torch.float64, device=dev)
+        _ffi.check(self.lib.isdf_tri_distance_tiles(_addr(p), n, _addr(qp), _addr(packed) if m else None, m, _addr(tiles),
+                                                    _addr(order_clean), n_tiles, float(beta), _addr(dist), _addr(index),
+                                                    _addr(closest), _addr(winding), _ffi.ptr(record), _ffi.ptr(stats), _ffi.ptr(ws),
+                                                    int(ws.numel()), _stream(dev)), "isdf_tri_distance_tiles")
+        return dist, index, closest, winding, record, stats
 
     # ---- frame-to-map pose alignment ---------------------------------------------------
     def _pose_args(self, name, depth, T_WC, cam, frame_of_pose, stride, min_depth, max_depth):
