@@ -1183,6 +1183,94 @@ int isdf_route_relax(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, in
 int isdf_route_trace(const int32_t* dist, int32_t nx, int32_t ny, int32_t nz, const int32_t* starts, int32_t B, int32_t max_len,
                      int32_t* path, int32_t* len, void* stream);
 
+/* ---- where to look next: frontier voxels, their connected components, and the view gain of a camera pose -----------------
+ * The map is incomplete; these calls say where its boundary is and how much unknown space a candidate pose would see.  The
+ * reference has no counterpart.  A STATE volume is u8 [nx][ny][nz], row-major, k fastest: ISDF_VOXEL_UNKNOWN, ISDF_VOXEL_FREE, and
+ * any value >= ISDF_VOXEL_OCCUPIED is occupied.  Dims follow routing's rule (every side >= 1, at most ISDF_ROUTE_MAX_VOXELS
+ * voxels).  p = (i * ny + j) * nz + k is a voxel's linear index.  Every output is an integer or one float32 produced by the
+ * sequence stated below: results are compared bit for bit and do not depend on the run.
+ *
+ * isdf_frontier_init: label[p] (device int32 [nx][ny][nz]) <- p where p is a frontier voxel, ISDF_FRONTIER_NONE elsewhere.  p
+ * is a frontier voxel iff state[p] == ISDF_VOXEL_FREE and at least one of its six face neighbours INSIDE the grid is
+ * ISDF_VOXEL_UNKNOWN; the outside of the grid is not unknown.  One launch.
+ *
+ * isdf_frontier_relax: `rounds` rounds of two launches each, label -> workspace -> label, every launch
+ *   out[p] = min(in[p], min over the 26 neighbours q inside the grid of in[q])     for in[p] < NONE;  NONE stays NONE
+ * applied tile by tile as isdf_route_relax applies its update (ISDF_ROUTE_TILE^3 voxels and a one-voxel halo, repeated inside the
+ * tile until it stops changing or a cap is reached).  Every value written is the index of a voxel of the same 26-connected
+ * component of frontier voxels and values only decrease, so the fixed point is THE LEAST LINEAR INDEX OF THE COMPONENT, whatever
+ * the tile, cap or number of launches.  changed: device int32 [rounds], zeroed by the call; changed[r] = 1 iff round r lowered
+ * any label.  No host synchronisation.
+ *
+ * isdf_frontier_clusters: a frontier voxel is one with 0 <= label[p] < NONE; q = label[p] is its root when q < nx*ny*nz and
+ * label[q] == q; a frontier voxel whose label is not a root is an ORPHAN (there is none on converged labels) and joins no record.
+ * counts (device int32 [3]) <- the number of roots, of frontier voxels, of orphans.  When roots <= max_clusters:
+ * records (device int64 [max_clusters][ISDF_FRONTIER_RECORD]), one row per root IN ASCENDING ORDER OF THE ROOT'S INDEX (positions
+ * from prefix sums, no atomic decides one):
+ *   root, count, sum_i, sum_j, sum_k, min_i, min_j, min_k, max_i, max_j, max_k, 0
+ * over the voxels of the root (integer atomics: sums, minima and maxima of integers are exact whatever the order).  Rows past
+ * the number of roots are not written.  With more roots than max_clusters the counts are written and the records are not: the
+ * caller sizes the records from counts[0] and calls again.  Four launches at most; max_clusters = 0 (records may be NULL) counts
+ * only.
+ *
+ * isdf_view_gain: B camera-to-world poses T_WC (device float [B][4][4], rows of 4), one ray per pixel (r, c) of an H x W image.
+ * origin, spacing: HOST float[3], voxel (i, j, k) centred at origin + (i, j, k) * spacing and covering [a - 0.5, a + 0.5) per axis
+ * in index coordinates.  All float32, every operation rounded on its own, nothing fused, IEEE division (T = T_WC[b]):
+ *   ray     x = ((float)c - cx) / fx,  y = ((float)r - cy) / fy                  (the reference's ray_dirs_C; t is z-depth)
+ *           dW_a = (T[a][0]*x + T[a][1]*y) + T[a][2];   e_a = T[a][3]
+ *           g0_a = (e_a - origin_a) / spacing_a;        dg_a = dW_a / spacing_a
+ *           any of g0, dg not finite: the ray MISSES (count 0, depth 0, no bits) -- a NaN pose is data, not an error
+ *   clip    t0 = t_min, t1 = t_max;  per axis a = 0, 1, 2 with n_a the side and hi_a = (float)n_a - 0.5f:
+ *             dg_a == 0:  miss if g0_a < -0.5f or g0_a >= hi_a
+ *             otherwise   ta = (-0.5f - g0_a) / dg_a,  tb = (hi_a - g0_a) / dg_a,
+ *                         t0 = max(t0, min(ta, tb)),   t1 = min(t1, max(ta, tb))
+ *           miss unless t0 < t1
+ *   start   c_a = (int)clamp(floorf((g0_a + t0*dg_a) + 0.5f), 0, (float)(n_a - 1))          (clamped before the cast)
+ *           step_a = dg_a > 0 ? 1 : -1;   inv_a = 1.0f / dg_a
+ *           tMax_a = (((float)c_a + 0.5f*(float)step_a) - g0_a) * inv_a,  +inf where dg_a == 0 (0 is never multiplied by inf);
+ *           tMax_a is RECOMPUTED FROM THE CELL by this formula after every step of axis a, never accumulated
+ *   walk    t_in = t0; at most nx + ny + nz times:
+ *             s = state[c];  s == UNKNOWN: count the voxel and set its bit;  s >= OCCUPIED: depth = t_in, stop
+ *             axis = the a with the least tMax_a, the lowest a on ties (y iff tMax_y < tMax_x; z iff tMax_z < the lesser of them)
+ *             t_in = tMax_axis;  stop unless t_in < t1;  c_axis += step_axis;  stop if the cell left the grid
+ * unknown (device int32 [B][H][W]) <- the count; depth (device float [B][H][W]) <- the z-depth at which the ray enters its first
+ * occupied voxel, 0 without one (a depth image of the voxel map).  distinct (device int32 [B], or NULL) <- the number of DISTINCT
+ * unknown voxels the rays of view b pass, through a bitmap of ceil(nx*ny*nz / 32) words per view in the workspace: zeroed by the
+ * call, set with atomic OR, counted by a popcount launch (integer atomics only).  distinct == NULL needs no workspace.  B = 0 is a
+ * no-op.  One launch, three with distinct; no host synchronisation.
+ *
+ * ISDF_EINVAL, before anything is launched: a NULL state / label / changed / counts / origin / spacing (records when
+ * max_clusters > 0; T_WC / unknown / depth when B > 0), a side < 1, more than ISDF_ROUTE_MAX_VOXELS voxels, rounds < 1,
+ * max_clusters < 0, B < 0, H or W < 1 (or H*W, or B * ceil(H/8) * ceil(W/8), beyond 2^31 - 1), a spacing that is not finite or
+ * <= 0, an origin that is not finite, fx or fy zero, an intrinsic that is not finite, t_min < 0 or NaN, t_max <= t_min or NaN
+ * (+inf is allowed).  ISDF_EWORKSPACE: a workspace that is NULL or smaller than the size query says (isdf_view_gain: only with
+ * distinct and B > 0). */
+#define ISDF_VOXEL_UNKNOWN 0
+#define ISDF_VOXEL_FREE 1
+#define ISDF_VOXEL_OCCUPIED 2
+#define ISDF_FRONTIER_NONE 1073741824       /* 2^30 */
+#define ISDF_FRONTIER_RECORD 12             /* int64 per cluster */
+
+int isdf_frontier_init(const uint8_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t* label, void* stream);
+
+/* up(4 * n) + up(4 * ceil(n / 256)), n = nx*ny*nz, up(x) = x rounded up to 256: one int32 volume (the ping-pong partner of label
+ * for isdf_frontier_relax, the roots' slots for isdf_frontier_clusters) and one int32 per 256 voxels (the prefix sums).
+ * ISDF_EINVAL for a side < 1 or more than ISDF_ROUTE_MAX_VOXELS voxels. */
+int64_t isdf_frontier_ws_bytes(int32_t nx, int32_t ny, int32_t nz);
+
+int isdf_frontier_relax(int32_t* label, int32_t nx, int32_t ny, int32_t nz, void* workspace, int64_t workspace_bytes, int32_t rounds,
+                        int32_t* changed, void* stream);
+
+int isdf_frontier_clusters(const int32_t* label, int32_t nx, int32_t ny, int32_t nz, void* workspace, int64_t workspace_bytes,
+                           int32_t max_clusters, int32_t* counts, int64_t* records, void* stream);
+
+/* up(4 * B * ceil(nx*ny*nz / 32)): the B bitmaps of isdf_view_gain's distinct count.  ISDF_EINVAL for bad dims or B < 0. */
+int64_t isdf_view_gain_ws_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t B);
+
+int isdf_view_gain(const uint8_t* state, int32_t nx, int32_t ny, int32_t nz, const float* origin, const float* spacing,
+                   const float* T_WC, int32_t B, float fx, float fy, float cx, float cy, int32_t H, int32_t W, float t_min, float t_max,
+                   int32_t* unknown, float* depth, int32_t* distinct, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,8 @@ EDT_NONE, EDT_MAX_SIDE = 1 << 30, 1024              # ISDF_EDT_NONE, ISDF_EDT_MA
 TRI_TILE, TRI_SLOT_FLOATS, TRI_RECORD = 256, 24, 4   # ISDF_TRI_TILE, ISDF_TRI_SLOT_FLOATS, ISDF_TRI_RECORD (doubles)
 TRI_TILE_RECORD = 16                                  # ISDF_TRI_TILE_RECORD (doubles per tile)
 ROUTE_NONE, ROUTE_MAX_VOXELS, ROUTE_TILE = 1 << 30, 1 << 27, 8    # ISDF_ROUTE_NONE, ISDF_ROUTE_MAX_VOXELS, ISDF_ROUTE_TILE
+VOXEL_UNKNOWN, VOXEL_FREE, VOXEL_OCCUPIED = 0, 1, 2          # ISDF_VOXEL_*: the states of a u8 state volume (>= 2 is occupied)
+FRONTIER_NONE, FRONTIER_RECORD = 1 << 30, 12                  # ISDF_FRONTIER_NONE, ISDF_FRONTIER_RECORD (int64 per cluster)
 FLAG_VIS_SDF, FLAG_VOX_SDF, FLAG_VIS_GRAD, FLAG_VOX_GRAD = 1, 2, 4, 8    # isdf_region_args.flags
 
 
@@ -248,6 +250,13 @@ PROTOTYPES = {
     "isdf_route_ws_bytes": (i64, [i32, i32, i32]),
     "isdf_route_relax": (C.c_int, [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp]),
     "isdf_route_trace": (C.c_int, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
+    "isdf_frontier_init": (C.c_int, [vp, i32, i32, i32, vp, vp]),
+    "isdf_frontier_ws_bytes": (i64, [i32, i32, i32]),
+    "isdf_frontier_relax": (C.c_int, [vp, i32, i32, i32, vp, i64, i32, vp, vp]),
+    "isdf_frontier_clusters": (C.c_int, [vp, i32, i32, i32, vp, i64, i32, vp, vp, vp]),
+    "isdf_view_gain_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "isdf_view_gain": (C.c_int, [vp, i32, i32, i32, P(f32), P(f32), vp, i32, f32, f32, f32, f32, i32, i32, f32, f32, vp, vp, vp, vp,
+                                 i64, vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
-SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "arm.hip", "fusion.hip", "tri.hip", "tri_tiles.hip", "route.hip", "capi.hip"]
+SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "arm.hip", "fusion.hip", "tri.hip", "tri_tiles.hip", "route.hip", "explore.hip", "capi.hip"]
 HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "block_reduce.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", "tri_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
@@ -51,6 +51,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-com
 # tri_tiles.hip: the same per-pair sequence (tri_dev.h) must give tri.hip's bits, so tri.hip's flags; its double rule and dipole
 # terms are restated by a float64 model operation for operation.
 # route.hip: int32 throughout, the default flags.
+# explore.hip: the voxel walk of isdf_view_gain is a stated fp32 sequence that a numpy model repeats bit for bit (every operation
+# rounded, no fused multiply-add); three axes through the same chain, visible.hip's shape.  Its label and cluster kernels are integer.
 PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"],
             "dw.hip": ["-fno-slp-vectorize"], "mesh.hip": ["-fno-slp-vectorize"],
             "render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "eval.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
@@ -59,7 +61,8 @@ PER_FILE = {"fwd_pair.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-thr
             "band.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "pose.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
             "traj.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "arm.hip": ["-fno-slp-vectorize", "-ffp-contract=off", "-mllvm", "-instcombine-max-copied-from-constant-users=100000"],
             "fusion.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
-            "tri.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "tri_tiles.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
+            "tri.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "tri_tiles.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
+            "explore.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -851,4 +851,55 @@ int isdf_route_trace(const int32_t* dist, int32_t nx, int32_t ny, int32_t nz, co
   return launch_route_trace(dist, nx, ny, nz, starts, B, max_len, path, len, (hipStream_t)stream);
 }
 
+// ---- where to look next: frontiers, clusters and view gain (explore.hip); the grids follow routing's rule
+int isdf_frontier_init(const uint8_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t* label, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!state || !label || !route_dims_ok(nx, ny, nz)) return ISDF_EINVAL;
+  return launch_frontier_init(state, nx, ny, nz, label, (hipStream_t)stream);
+}
+
+int64_t isdf_frontier_ws_bytes(int32_t nx, int32_t ny, int32_t nz) {
+  return route_dims_ok(nx, ny, nz) ? frontier_ws_bytes(nx, ny, nz) : ISDF_EINVAL;
+}
+
+int isdf_frontier_relax(int32_t* label, int32_t nx, int32_t ny, int32_t nz, void* workspace, int64_t workspace_bytes, int32_t rounds,
+                        int32_t* changed, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!label || !changed || !route_dims_ok(nx, ny, nz) || rounds < 1) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_frontier_ws_bytes(nx, ny, nz)) return ISDF_EWORKSPACE;
+  return launch_frontier_relax(label, nx, ny, nz, (int32_t*)workspace, rounds, changed, (hipStream_t)stream);
+}
+
+int isdf_frontier_clusters(const int32_t* label, int32_t nx, int32_t ny, int32_t nz, void* workspace, int64_t workspace_bytes,
+                           int32_t max_clusters, int32_t* counts, int64_t* records, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!label || !counts || !route_dims_ok(nx, ny, nz) || max_clusters < 0 || (max_clusters > 0 && !records)) return ISDF_EINVAL;
+  if (!workspace || workspace_bytes < isdf_frontier_ws_bytes(nx, ny, nz)) return ISDF_EWORKSPACE;
+  return launch_frontier_clusters(label, nx, ny, nz, workspace, max_clusters, counts, records, (hipStream_t)stream);
+}
+
+int64_t isdf_view_gain_ws_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t B) {
+  if (!route_dims_ok(nx, ny, nz) || B < 0) return ISDF_EINVAL;
+  return (4 * view_gain_words(nx, ny, nz) * B + 255) / 256 * 256;
+}
+
+int isdf_view_gain(const uint8_t* state, int32_t nx, int32_t ny, int32_t nz, const float* origin, const float* spacing,
+                   const float* T_WC, int32_t B, float fx, float fy, float cx, float cy, int32_t H, int32_t W, float t_min, float t_max,
+                   int32_t* unknown, float* depth, int32_t* distinct, void* workspace, int64_t workspace_bytes, void* stream) {
+  isdf_clear_stale_hip_error();
+  if (!state || !origin || !spacing || !route_dims_ok(nx, ny, nz) || B < 0 || H < 1 || W < 1) return ISDF_EINVAL;
+  if (B > 0 && (!T_WC || !unknown || !depth)) return ISDF_EINVAL;
+  // one wave per 8 x 8 pixel tile, four to a block; the outputs are indexed in 64 bits
+  if ((int64_t)H * W > 0x7fffffff || (int64_t)B * (((int64_t)H + 7) / 8) * (((int64_t)W + 7) / 8) > 0x7fffffff) return ISDF_EINVAL;
+  for (int k = 0; k < 3; ++k)
+    if (!(spacing[k] > 0.f) || !__builtin_isfinite(spacing[k]) || !__builtin_isfinite(origin[k])) return ISDF_EINVAL;
+  if (fx == 0.f || fy == 0.f) return ISDF_EINVAL;
+  for (float v : {fx, fy, cx, cy})
+    if (!__builtin_isfinite(v)) return ISDF_EINVAL;
+  if (!(t_min >= 0.f) || !(t_max > t_min)) return ISDF_EINVAL;      // also refuses NaN; t_max may be +inf
+  if (distinct && B > 0 && (!workspace || workspace_bytes < isdf_view_gain_ws_bytes(nx, ny, nz, B))) return ISDF_EWORKSPACE;
+  return launch_view_gain(state, nx, ny, nz, origin, spacing, T_WC, B, fx, fy, cx, cy, H, W, t_min, t_max, unknown, depth, distinct,
+                          workspace, (hipStream_t)stream);
+}
+
 }  // extern "C"

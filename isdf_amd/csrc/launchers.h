@@ -92,5 +92,15 @@ int launch_route_relax(const uint8_t* free, int32_t nx, int32_t ny, int32_t nz, 
                        int32_t* changed, hipStream_t st);
 int launch_route_trace(const int32_t* dist, int32_t nx, int32_t ny, int32_t nz, const int32_t* starts, int32_t B, int32_t max_len,
                        int32_t* path, int32_t* len, hipStream_t st);
+int launch_frontier_init(const uint8_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t* label, hipStream_t st);   // explore.hip
+int64_t frontier_ws_bytes(int32_t nx, int32_t ny, int32_t nz);
+int launch_frontier_relax(int32_t* label, int32_t nx, int32_t ny, int32_t nz, int32_t* ws, int32_t rounds, int32_t* changed,
+                          hipStream_t st);
+int launch_frontier_clusters(const int32_t* label, int32_t nx, int32_t ny, int32_t nz, void* ws, int32_t max_clusters, int32_t* counts,
+                             int64_t* records, hipStream_t st);
+int64_t view_gain_words(int32_t nx, int32_t ny, int32_t nz);
+int launch_view_gain(const uint8_t* state, int32_t nx, int32_t ny, int32_t nz, const float* origin, const float* spacing,
+                     const float* T_WC, int32_t B, float fx, float fy, float cx, float cy, int32_t H, int32_t W, float t_min,
+                     float t_max, int32_t* unknown, float* depth, int32_t* distinct, void* ws, hipStream_t st);
 
 }  // namespace isdf

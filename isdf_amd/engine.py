@@ -975,6 +975,89 @@ class Engine:
                                                  _ffi.ptr(length), _stream(self.device)), "isdf_route_trace")
         return path, length
 
+    # ---- where to look next: frontiers, clusters, view gain -------------------------------
+    def _frontier_ws(self, dims):
+        return self._scratch("frontier", int(self.lib.isdf_frontier_ws_bytes(*dims)))
+
+    def frontier_init(self, state, out=None):
+        """label int32 [nx,ny,nz] on the device: isdf_frontier_init -- the voxel's own linear index (i * ny + j) * nz + k where it is
+        a frontier voxel (FREE with at least one of its six face neighbours inside the grid UNKNOWN), _ffi.FRONTIER_NONE (2^30)
+        elsewhere.  state: contiguous uint8 [nx,ny,nz] on this device (_ffi.VOXEL_*; >= 2 is occupied).  out: a label volume to
+        overwrite.  No host synchronisation."""
+        s, dims = self._route_volume("frontier_init", "state", state, torch.uint8)
+        if out is None:
+            out = torch.empty(dims, dtype=torch.int32, device=self.device)
+        elif self._route_volume("frontier_init", "out", out, torch.int32)[1] != dims:
+            raise ValueError("frontier_init: out is %s, state %s" % (tuple(out.shape), dims))
+        _ffi.check(self.lib.isdf_frontier_init(_ffi.ptr(s), dims[0], dims[1], dims[2], _ffi.ptr(out), _stream(self.device)),
+                   "isdf_frontier_init")
+        return out
+
+    def frontier_relax(self, label, rounds=1, changed=None):
+        """changed int32 [rounds] on the device: isdf_frontier_relax -- `rounds` rounds (two tile launches each) of label[p] <-
+        min over p and its 26 neighbours, IN PLACE, for voxels below FRONTIER_NONE; changed[r] = 1 iff round r lowered any label.
+        Once a round changes nothing every frontier voxel holds the least linear index of its 26-connected component.  changed:
+        an int32 tensor of at least `rounds` elements to reuse.  The workspace is kept across calls.  No host synchronisation:
+        the caller decides when to look (isdf_amd.explore.frontiers does)."""
+        l, dims = self._route_volume("frontier_relax", "label", label, torch.int32)
+        rounds = int(rounds)
+        if rounds < 1:
+            raise ValueError("frontier_relax: rounds >= 1 (got %d)" % rounds)
+        if changed is None:
+            changed = torch.empty(rounds, dtype=torch.int32, device=self.device)
+        elif changed.dtype != torch.int32 or changed.numel() < rounds or not changed.is_contiguous():
+            raise ValueError("frontier_relax: changed must be a contiguous int32 tensor of at least %d elements" % rounds)
+        else:
+            self._check_device("frontier_relax", "changed", changed)
+        ws = self._frontier_ws(dims)
+        _ffi.check(self.lib.isdf_frontier_relax(_ffi.ptr(l), dims[0], dims[1], dims[2], _ffi.ptr(ws), int(ws.numel()), rounds,
+                                                _ffi.ptr(changed), _stream(self.device)), "isdf_frontier_relax")
+        return changed.reshape(-1)[:rounds]
+
+    def frontier_clusters(self, label, max_clusters):
+        """(counts int32 [3], records int64 [max_clusters, 12]) on the device: isdf_frontier_clusters -- counts = the number of
+        roots (label[p] == p), of frontier voxels, and of orphans (frontier voxels whose label is not a root: 0 on converged
+        labels); records, one row per root in ascending order of the root's index, = root, count, sum_i, sum_j, sum_k, min_i,
+        min_j, min_k, max_i, max_j, max_k, 0 over the root's voxels.  With more roots than max_clusters the counts are written
+        and the records are not (isdf_amd.explore.clusters then calls once more); rows past the number of roots are not written.
+        The workspace is kept across calls.  No host synchronisation."""
+        l, dims = self._route_volume("frontier_clusters", "label", label, torch.int32)
+        max_clusters = int(max_clusters)
+        if max_clusters < 0:
+            raise ValueError("frontier_clusters: max_clusters >= 0 (got %d)" % max_clusters)
+        counts = torch.empty(3, dtype=torch.int32, device=self.device)
+        records = torch.empty(max_clusters, _ffi.FRONTIER_RECORD, dtype=torch.int64, device=self.device)
+        ws = self._frontier_ws(dims)
+        _ffi.check(self.lib.isdf_frontier_clusters(_ffi.ptr(l), dims[0], dims[1], dims[2], _ffi.ptr(ws), int(ws.numel()),
+                                                   max_clusters, _ffi.ptr(counts), _addr(records), _stream(self.device)),
+                   "isdf_frontier_clusters")
+        return counts, records
+
+    def view_gain(self, state, origin, spacing, T_WC, cam, H, W, t_min=0.0, t_max=float("inf"), distinct=True):
+        """(unknown int32 [B,H,W], depth float32 [B,H,W], distinct int32 [B] or None) on the device: isdf_view_gain -- for the B
+        camera-to-world poses T_WC [B,4,4] one ray per pixel walks the voxels of `state` (contiguous uint8 [nx,ny,nz]; voxel
+        (i, j, k) centred at origin + (i, j, k) * spacing) from z-depth t_min to t_max or its first occupied voxel: unknown = the
+        UNKNOWN voxels it passes, depth = the z-depth at which it enters the occupied one (0 without), distinct = the number of
+        different unknown voxels the rays of a view pass.  A fixed fp32 sequence per ray (include/isdf_hip.h): equal to
+        tests/explore_model.py bit for bit.  cam: anything with fx, fy, cx, cy.  The bitmap workspace of `distinct` (one bit per
+        voxel and view) is kept across calls.  No host synchronisation."""
+        s, dims = self._route_volume("view_gain", "state", state, torch.uint8)
+        T = self._flat(torch.as_tensor(T_WC), torch.float32, 16)
+        B, H, W = int(T.shape[0]), int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError("view_gain: H and W >= 1 (got %d, %d)" % (H, W))
+        o = (C.c_float * 3)(*[float(v) for v in np.asarray(origin, np.float64).reshape(3)])
+        sp = (C.c_float * 3)(*[float(v) for v in np.asarray(spacing, np.float64).reshape(3)])
+        unknown = torch.empty(B, H, W, dtype=torch.int32, device=self.device)
+        depth = torch.empty(B, H, W, dtype=torch.float32, device=self.device)
+        count = torch.empty(B, dtype=torch.int32, device=self.device) if distinct else None
+        ws = self._scratch("view_gain", int(self.lib.isdf_view_gain_ws_bytes(dims[0], dims[1], dims[2], B))) if distinct and B else None
+        _ffi.check(self.lib.isdf_view_gain(_ffi.ptr(s), dims[0], dims[1], dims[2], o, sp, _addr(T), B, float(cam.fx), float(cam.fy),
+                                           float(cam.cx), float(cam.cy), H, W, float(t_min), float(t_max), _addr(unknown),
+                                           _addr(depth), _addr(count), _ffi.ptr(ws), int(ws.numel()) if ws is not None else 0,
+                                           _stream(self.device)), "isdf_view_gain")
+        return unknown, depth, count
+
     # ---- ground truth from a triangle mesh ------------------------------------------------
     def tri_pack(self, vertices, faces, transform=None):
         """(packed f32 [slots, 24], counts i32 [2], m) on the device: isdf_tri_pack, the mesh gathered once into the layout

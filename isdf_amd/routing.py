@@ -91,11 +91,14 @@ class _Scratch:
     def reserve(self, n):
         if self.changed is None or self.changed.numel() < n:
             self.changed = torch.empty(n, dtype=torch.int32, device=self.device)
-            self.pinned = torch.empty(n, dtype=torch.int32, pin_memory=True)
+            self.pinned = torch.empty(n, dtype=torch.int32, pin_memory=True) if self.device.type == "cuda" else None
         return self.changed[:n]
 
     def fetch(self, changed):
-        """the flags on the host: ONE copy into the pinned buffer, then the stream's end"""
+        """the flags on the host: ONE copy into the pinned buffer, then the stream's end (a host-side stand-in for an Engine, as
+        the CPU tests use, has its flags on the host already)"""
+        if self.pinned is None:
+            return changed.numpy().copy()
         host = self.pinned[:changed.numel()]
         host.copy_(changed, non_blocking=True)
         torch.cuda.current_stream(changed.device).synchronize()
@@ -107,7 +110,7 @@ _SCRATCH = {}
 
 def _scratch(device):
     device = torch.device(device)
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = "cpu" if device.type != "cuda" else device.index if device.index is not None else torch.cuda.current_device()
     s = _SCRATCH.get(key)
     if s is None:
         s = _SCRATCH[key] = _Scratch(device)
