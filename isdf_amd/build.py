@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libisdf_hip.so")
 SOURCES = ["chain.hip", "fwd_pair.hip", "dw.hip", "sampler.hip", "optim.hip", "ingest.hip", "mesh.hip", "render.hip", "eval.hip", "reduce.hip", "slices.hip", "visible.hip", "band.hip", "pose.hip", "traj.hip", "arm.hip", "fusion.hip", "tri.hip", "tri_tiles.hip", "route.hip", "explore.hip", "capi.hip"]
-HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "block_reduce.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", "tri_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
+HEADERS = ["isdf_common.h", "launchers.h", "block_scan.h", "block_reduce.h", "mc_tables.h", "chain_params.h", "chain_dev.h", "chain_debug.h", "gt_volume_dev.h", "tri_dev.h", "descent_dev.h", os.path.join("..", "..", "include", "isdf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-command-line-argument",
          "-fno-gpu-rdc"] + os.environ.get("ISDF_EXTRA_HIPCC_FLAGS", "").split()
 

@@ -10,9 +10,10 @@
 //        operations on the same values: the same bits), so no per-sample value crosses threads and nothing waits.
 //        grad_t goes to LDS; the scalar sums, minimum and counts stay in registers
 //     2  the record's sums: lanes by shuffle, the four waves in wave order (block_reduce.h)
-//     3  (moving trajectories only) K^-1 grad by the closed-form inverse, one lane per joint, as traj.hip; then the projected
-//        step Delta', its infinity norm m and the number of clamped entries over all threads
+//     3  (moving trajectories only) K^-1 grad by the closed-form inverse, one lane per joint; then the projected step Delta',
+//        its infinity norm m and the number of clamped entries over all threads
 //     4  state, record, the new theta and the query points of the theta the call leaves (the frames once more)
+//   The cost, the sums, the solve, the state rule and the record are descent_dev.h's, shared with traj.hip.
 // LDS: 2 J doubles per waypoint (grad / y / Delta', and P), allocated per launch: 16 J T bytes, 48 KB at J = 8 and
 // ISDF_ARM_MAX_WAYPOINTS = 384 -- traj.hip's ceiling, which leaves the 64 KB a workgroup may ask for without an opt-in room for
 // the 44 doubles of scalars.  Planes of T doubles per joint: a wave's 64 consecutive waypoints are 64 consecutive doubles.
@@ -22,10 +23,10 @@
 #include "isdf_common.h"
 #include "launchers.h"
 #include "block_reduce.h"
+#include "descent_dev.h"
 
 namespace isdf {
 
-constexpr int AREC = ISDF_TRAJ_RECORD;
 constexpr int AJ = ISDF_ARM_MAX_JOINTS;
 constexpr int AS = ISDF_ARM_MAX_SPHERES;
 
@@ -147,14 +148,7 @@ __device__ __forceinline__ void arm_sample(const float* qb, const float* __restr
   o.c = 0.0; o.cp = 0.0; o.sigma = 0.0;
   o.h[0] = 0.0; o.h[1] = 0.0; o.h[2] = 0.0;
   if (o.bad || !interior) return;
-  if (o.d < 0.0) {
-    o.c = -o.d + eps * 0.5;
-    o.cp = -1.0;
-  } else if (o.d <= eps) {
-    const double u = o.d - eps;
-    o.c = (u * u) / (2.0 * eps);
-    o.cp = u / eps;
-  }
+  descent_cost(o.d, eps, o.c, o.cp);
   const int64_t ip = (i + S) * 3, im = (i - S) * 3;
   const double v0 = ((double)qb[ip] - (double)qb[im]) * 0.5, v1 = ((double)qb[ip + 1] - (double)qb[im + 1]) * 0.5,
                v2 = ((double)qb[ip + 2] - (double)qb[im + 2]) * 0.5;
@@ -168,7 +162,7 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
                                                        const float* q, const float* __restrict__ sdf, const float* __restrict__ grad,
                                                        double* __restrict__ records, float* q_out, double* __restrict__ grad_out) {
   extern __shared__ double lds[];         // gy [J][T]: grad_t, then y_t, then Delta'_t;  P [J][T]
-  __shared__ double sh[4][9];
+  __shared__ double sh[4][DSLOTS];
   __shared__ double shm[4];
   const int T = p.T, J = p.J, S = p.S, n = T - 2, tid = threadIdx.x;
   double* gy = lds;
@@ -181,7 +175,7 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
   const int state_in = state[b];
   const double eps = (double)p.eps, w_obs = (double)p.w_obs, ws = (double)p.w_smooth * (double)(T - 1);
 
-  double f_obs = 0.0, seg2 = 0.0, len = 0.0, gsq = 0.0, mind = (double)INFINITY, n_neg = 0.0, n_act = 0.0, n_bad = 0.0;
+  DescentSums sums;
   for (int t = tid; t < T; t += 256) {
     const bool interior = t > 0 && t < T - 1;
     double th[AJ], gt[AJ];                 // gt: the smoothness term first, then grad_t
@@ -199,8 +193,8 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
       }
     }
     if (t < T - 1) {
-      seg2 += qd;
-      len += sqrt(qd);
+      sums.seg2 += qd;
+      sums.len += sqrt(qd);
     }
 
     double Rl[AJ][3], Ml[AJ][3];            // per link 1 .. J: sum r, sum q x r
@@ -215,12 +209,10 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
       ArmSample me;
       arm_sample(qb, sdfb, gradb, t, s, S, eps, rad, interior, me);
       if (me.bad) {
-        n_bad += (double)me.bad;
+        sums.n_bad += (double)me.bad;
         continue;
       }
-      mind = fmin(mind, me.d);
-      n_neg += me.d < 0.0 ? 1.0 : 0.0;
-      n_act += me.d < eps ? 1.0 : 0.0;
+      sums.clearance(me.d, eps);
       if (!interior) continue;
       fo = fo + me.c * me.sigma;
       ArmSample lo, hi;                     // the neighbours in t: c = 0 and h = 0 at a fixed waypoint and for a bad sample
@@ -244,7 +236,7 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
 
     double g2 = 0.0;
     if (interior) {
-      f_obs += fo;
+      sums.f_obs += fo;
 #pragma unroll
       for (int j = AJ - 2; j >= 0; --j) {                 // suffix sums over the links, in place
         if (j + 1 < J) {
@@ -266,7 +258,7 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
 #pragma unroll
       for (int j = 0; j < AJ; ++j)
         if (j < J) g2 = g2 + gt[j] * gt[j];
-      gsq += g2;
+      sums.gsq += g2;
     }
 #pragma unroll
     for (int j = 0; j < AJ; ++j) {
@@ -277,38 +269,11 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
     }
   }
 
-  const int wave = tid >> 6, lane = tid & 63;
-  {
-    const double v0 = wave_reduce<RedSum>(f_obs), v1 = wave_reduce<RedSum>(seg2), v2 = wave_reduce<RedMin>(mind),
-                 v3 = wave_reduce<RedSum>(n_neg), v4 = wave_reduce<RedSum>(n_act), v5 = wave_reduce<RedSum>(gsq),
-                 v6 = wave_reduce<RedSum>(n_bad), v7 = wave_reduce<RedSum>(len);
-    if (lane == 0) {
-      sh[wave][0] = v0; sh[wave][1] = v1; sh[wave][2] = v2; sh[wave][3] = v3;
-      sh[wave][4] = v4; sh[wave][5] = v5; sh[wave][6] = v6; sh[wave][7] = v7;
-    }
-  }
-  __syncthreads();                        // sh, and every grad_t in gy; every read of q is complete
-  const auto sum4 = [&](int v) { return waves_combine<RedSum>(sh[0][v], sh[1][v], sh[2][v], sh[3][v]); };
-  const double bad_total = sum4(6);
+  const double bad_total = descent_reduce(sums, sh);          // a barrier: sh, and every grad_t in gy; every read of q is complete
 
   double m = 0.0, n_cut = 0.0;
   if (state_in == 0) {                    // uniform over the workgroup
-    if (tid < J) {
-      double* P = Pp + tid * T;
-      double* g = gy + tid * T;
-      double acc = 0.0;
-      for (int i = 1; i <= n; ++i) {
-        acc = acc + (double)i * g[i];
-        P[i] = acc;
-      }
-      acc = 0.0;
-      const double n1 = (double)(n + 1);
-      for (int i = n; i >= 1; --i) {
-        const double gi = g[i], w = (double)(n + 1 - i);
-        g[i] = (w * P[i] + (double)i * acc) / n1;
-        acc = acc + w * gi;
-      }
-    }
+    if (tid < J) descent_solve(gy + tid * T, Pp + tid * T, n);
     __syncthreads();
     const double scale = (double)p.eta * (double)(T - 1);
     for (int t = tid; t < T; t += 256) {
@@ -331,46 +296,22 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
     }
     m = wave_reduce<RedMax>(m);
     n_cut = wave_reduce<RedSum>(n_cut);
-    if (lane == 0) {
-      shm[wave] = m;
-      sh[wave][8] = n_cut;
+    if ((tid & 63) == 0) {                // lane 0 of each wave
+      shm[tid >> 6] = m;
+      sh[tid >> 6][8] = n_cut;
     }
     __syncthreads();
     m = waves_combine<RedMax>(shm[0], shm[1], shm[2], shm[3]);
-    n_cut = sum4(8);
+    n_cut = descent_sum4(sh, 8);
   }
 
-  int state_out = state_in;
-  double kappa = 0.0;
-  if (state_in == 0) {
-    if (bad_total > 0.0) state_out = 2;
-    else if (m < (double)p.tol) state_out = 1;
-    else kappa = m <= (double)p.max_step ? 1.0 : (double)p.max_step / m;
-  }
-  const bool apply = state_in == 0 && state_out == 0;
-
-  if (tid < AREC) {
-    double v = 0.0;
-    if (tid == 2) v = waves_combine<RedMin>(sh[0][2], sh[1][2], sh[2][2], sh[3][2]);
-    else if (tid == 0) v = sum4(0);
-    else if (tid == 1) v = (0.5 * (double)(T - 1)) * sum4(1);
-    else if (tid == 3) v = sum4(3);
-    else if (tid == 4) v = sum4(4);
-    else if (tid == 5) v = sum4(5);
-    else if (tid == 6) v = m;
-    else if (tid == 7) v = kappa;
-    else if (tid == 8) v = bad_total;
-    else if (tid == 9) v = (double)state_out;
-    else if (tid == 10) v = sum4(7);
-    else if (tid == 11) v = n_cut;
-    records[b * AREC + tid] = v;
-  }
-  if (tid == 0 && state_out != state_in) state[b] = state_out;
+  const DescentClose cl = descent_close(state_in, bad_total, m, (double)p.tol, (double)p.max_step);
+  descent_record(sh, T, m, bad_total, state_in, cl, n_cut, records + b * DREC, state + b);
 
   // every read of theta's neighbours and of q lies before the barriers above: thread t now rewrites row t alone
-  if (!apply && !q_out) return;
+  if (!cl.apply && !q_out) return;
   for (int t = tid; t < T; t += 256) {
-    const bool move = apply && t > 0 && t < T - 1;
+    const bool move = cl.apply && t > 0 && t < T - 1;
     double th[AJ];
 #pragma unroll
     for (int j = 0; j < AJ; ++j) {
@@ -378,7 +319,7 @@ __global__ __launch_bounds__(256) void arm_step_kernel(const ArmParams p, const 
       if (j < J) {
         float y = thb[t * J + j];
         if (move) {
-          y = (float)((double)y + kappa * gy[j * T + t]);
+          y = (float)((double)y + cl.kappa * gy[j * T + t]);
           thb[t * J + j] = y;
         }
         th[j] = (double)y;

@@ -663,6 +663,13 @@ static bool traj_args_ok(const isdf_traj_args* a) {
   return true;
 }
 
+// the six parameters of a descent step, isdf_traj_step's and isdf_arm_step's alike
+static bool descent_params_ok(float eps, float w_obs, float w_smooth, float eta, float max_step, float tol) {
+  for (float v : {w_obs, w_smooth, tol})
+    if (!(v >= 0.f) || !__builtin_isfinite(v)) return false;
+  return eps > 0.f && eta > 0.f && max_step > 0.f && __builtin_isfinite(eps) && __builtin_isfinite(eta);   // no NaN; max_step may be +inf
+}
+
 int isdf_traj_points(const isdf_traj_args* a, float* q_out, void* stream) {
   isdf_clear_stale_hip_error();
   if (!traj_args_ok(a) || !q_out) return ISDF_EINVAL;
@@ -673,10 +680,7 @@ int isdf_traj_step(const isdf_traj_args* a, const float* sdf, const float* grad,
                    void* stream) {
   isdf_clear_stale_hip_error();
   if (!traj_args_ok(a) || !a->state || !sdf || !grad || !records) return ISDF_EINVAL;
-  if (!(a->eps > 0.f) || !(a->eta > 0.f) || !(a->max_step > 0.f)) return ISDF_EINVAL;                  // also refuses NaN
-  if (!__builtin_isfinite(a->eps) || !__builtin_isfinite(a->eta)) return ISDF_EINVAL;                   // max_step may be +inf
-  for (float v : {a->w_obs, a->w_smooth, a->tol})
-    if (!(v >= 0.f) || !__builtin_isfinite(v)) return ISDF_EINVAL;
+  if (!descent_params_ok(a->eps, a->w_obs, a->w_smooth, a->eta, a->max_step, a->tol)) return ISDF_EINVAL;
   return launch_traj_step(*a, sdf, grad, records, q_out, grad_out, (hipStream_t)stream);
 }
 
@@ -719,10 +723,7 @@ int isdf_arm_step(const isdf_arm_args* a, const float* q, const float* sdf, cons
                   double* grad_out, void* stream) {
   isdf_clear_stale_hip_error();
   if (!arm_args_ok(a) || !a->state || !q || !sdf || !grad || !records) return ISDF_EINVAL;
-  if (!(a->eps > 0.f) || !(a->eta > 0.f) || !(a->max_step > 0.f)) return ISDF_EINVAL;                  // also refuses NaN
-  if (!__builtin_isfinite(a->eps) || !__builtin_isfinite(a->eta)) return ISDF_EINVAL;                   // max_step may be +inf
-  for (float v : {a->w_obs, a->w_smooth, a->tol})
-    if (!(v >= 0.f) || !__builtin_isfinite(v)) return ISDF_EINVAL;
+  if (!descent_params_ok(a->eps, a->w_obs, a->w_smooth, a->eta, a->max_step, a->tol)) return ISDF_EINVAL;
   return launch_arm_step(*a, q, sdf, grad, records, q_out, grad_out, (hipStream_t)stream);
 }
 

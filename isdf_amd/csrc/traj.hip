@@ -8,20 +8,21 @@
 //     1  thread k takes waypoints k, k + 256, ..: its S samples (s ascending) give C_t and G_t, its neighbours in x the speed;
 //        C_t vh_t and sigma_t G_t go to LDS, the scalar sums, minimum and counts stay in registers
 //     2  grad_t from the neighbours' C vh in LDS; the record's sums: lanes by shuffle, the four waves in wave order
-//     3  (moving trajectories only) K^-1 grad by the closed-form inverse: two ordered prefix sums, one lane per coordinate --
-//        2 (T-2) dependent adds, no division on the chain --, then m = max |Delta_t| over all threads
+//     3  (moving trajectories only) K^-1 grad by the closed-form inverse, one lane per coordinate, then m = max |Delta_t| over
+//        all threads
 //     4  state, record, the new x and the next iteration's query points
+//   The cost, the sums, the solve, the state rule and the record are descent_dev.h's, shared with arm.hip.
 // LDS: 6 doubles per waypoint, allocated per launch for the T of the call (48 T bytes: 3 KB at T = 64, 48 KB at T = 1024), and
-// 36 doubles of scalars, so that short trajectories share a CU up to the wave limit.  Coordinates are planes of T doubles: a
+// 40 doubles of scalars, so that short trajectories share a CU up to the wave limit.  Coordinates are planes of T doubles: a
 // wave's 64 consecutive waypoints are 64 consecutive doubles, conflict-free.  Offsets and radii are launch arguments (512 B).
 // Nothing is indexed dynamically in registers: no scratch.
 #include "isdf_common.h"
 #include "launchers.h"
 #include "block_reduce.h"
+#include "descent_dev.h"
 
 namespace isdf {
 
-constexpr int TREC = ISDF_TRAJ_RECORD;
 constexpr int TMAXS = ISDF_TRAJ_MAX_SPHERES;
 
 struct TrajBody {
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
                                                         const float* __restrict__ grad, double* __restrict__ records,
                                                         float* __restrict__ q_out, double* __restrict__ grad_out) {
   extern __shared__ double lds[];         // cv [3][T]: C_t vh_t, then P;  nab [3][T]: sigma_t G_t, then grad_t, then y_t
-  __shared__ double sh[4][8];
+  __shared__ double sh[4][DSLOTS];
   __shared__ double shm[4];
   const int T = p.T, S = p.S, n = T - 2, tid = threadIdx.x;
   double* cv = lds;
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
   const int state_in = state[b];
   const double eps = (double)p.eps, w_obs = (double)p.w_obs, ws = (double)p.w_smooth * (double)(T - 1);
 
-  double f_obs = 0.0, seg2 = 0.0, len = 0.0, gsq = 0.0, mind = (double)INFINITY, n_neg = 0.0, n_act = 0.0, n_bad = 0.0;
+  DescentSums sums;
   for (int t = tid; t < T; t += 256) {
     const bool interior = t > 0 && t < T - 1;
     double C = 0.0, G0 = 0.0, G1 = 0.0, G2 = 0.0;
@@ -71,22 +72,13 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
       const double g0 = (double)grad[(i0 + s) * 3], g1 = (double)grad[(i0 + s) * 3 + 1], g2 = (double)grad[(i0 + s) * 3 + 2];
       const int bad = (isfinite(sd) ? 0 : 1) + (isfinite(g0) ? 0 : 1) + (isfinite(g1) ? 0 : 1) + (isfinite(g2) ? 0 : 1);
       if (bad) {
-        n_bad += (double)bad;
+        sums.n_bad += (double)bad;
         continue;
       }
       const double d = sd - (double)body.rad[s];
-      mind = fmin(mind, d);
-      n_neg += d < 0.0 ? 1.0 : 0.0;
-      n_act += d < eps ? 1.0 : 0.0;
-      double c = 0.0, cp = 0.0;
-      if (d < 0.0) {
-        c = -d + eps * 0.5;
-        cp = -1.0;
-      } else if (d <= eps) {
-        const double u = d - eps;
-        c = (u * u) / (2.0 * eps);
-        cp = u / eps;
-      }
+      sums.clearance(d, eps);
+      double c, cp;
+      descent_cost(d, eps, c, cp);
       if (interior) {
         C += c;
         G0 += cp * g0;
@@ -98,8 +90,8 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
     if (t < T - 1) {
       const double e0 = (double)xb[t * 3 + 3] - c0, e1 = (double)xb[t * 3 + 4] - c1, e2 = (double)xb[t * 3 + 5] - c2;
       const double q = (e0 * e0 + e1 * e1) + e2 * e2;
-      seg2 += q;
-      len += sqrt(q);
+      sums.seg2 += q;
+      sums.len += sqrt(q);
     }
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
     if (interior) {
@@ -110,7 +102,7 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
       const double h0 = go ? v0 / sigma : 0.0, h1 = go ? v1 / sigma : 0.0, h2 = go ? v2 / sigma : 0.0;
       a0 = C * h0; a1 = C * h1; a2 = C * h2;
       s0 = sigma * G0; s1 = sigma * G1; s2 = sigma * G2;
-      f_obs += C * sigma;
+      sums.f_obs += C * sigma;
     }
     cv[t] = a0; cv[T + t] = a1; cv[2 * T + t] = a2;
     nab[t] = s0; nab[T + t] = s1; nab[2 * T + t] = s2;
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
       r0 = w_obs * o0 + ws * m0;
       r1 = w_obs * o1 + ws * m1;
       r2 = w_obs * o2 + ws * m2;
-      gsq += (r0 * r0 + r1 * r1) + r2 * r2;
+      sums.gsq += (r0 * r0 + r1 * r1) + r2 * r2;
     }
     nab[t] = r0; nab[T + t] = r1; nab[2 * T + t] = r2;        // only waypoint t's own entries of nab are read above
     if (grad_out) {
@@ -137,38 +129,11 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
     }
   }
 
-  const int wave = tid >> 6, lane = tid & 63;
-  {
-    const double v0 = wave_reduce<RedSum>(f_obs), v1 = wave_reduce<RedSum>(seg2), v2 = wave_reduce<RedMin>(mind),
-                 v3 = wave_reduce<RedSum>(n_neg), v4 = wave_reduce<RedSum>(n_act), v5 = wave_reduce<RedSum>(gsq),
-                 v6 = wave_reduce<RedSum>(n_bad), v7 = wave_reduce<RedSum>(len);
-    if (lane == 0) {
-      sh[wave][0] = v0; sh[wave][1] = v1; sh[wave][2] = v2; sh[wave][3] = v3;
-      sh[wave][4] = v4; sh[wave][5] = v5; sh[wave][6] = v6; sh[wave][7] = v7;
-    }
-  }
-  __syncthreads();                        // sh, and every grad_t in nab; cv is free from here
-  const auto sum4 = [&](int v) { return waves_combine<RedSum>(sh[0][v], sh[1][v], sh[2][v], sh[3][v]); };
-  const double bad_total = sum4(6);
+  const double bad_total = descent_reduce(sums, sh);          // a barrier: sh, and every grad_t in nab; cv is free from here
 
   double m = 0.0;
   if (state_in == 0) {                    // uniform over the workgroup
-    if (tid < 3) {
-      double* P = cv + tid * T;
-      double* g = nab + tid * T;
-      double acc = 0.0;
-      for (int i = 1; i <= n; ++i) {
-        acc = acc + (double)i * g[i];
-        P[i] = acc;
-      }
-      acc = 0.0;
-      const double n1 = (double)(n + 1);
-      for (int i = n; i >= 1; --i) {
-        const double gi = g[i], w = (double)(n + 1 - i);
-        g[i] = (w * P[i] + (double)i * acc) / n1;
-        acc = acc + w * gi;
-      }
-    }
+    if (tid < 3) descent_solve(nab + tid * T, cv + tid * T, n);
     __syncthreads();
     const double scale = (double)p.eta * (double)(T - 1);
     for (int t = tid; t < T; t += 256) {
@@ -180,45 +145,22 @@ __global__ __launch_bounds__(256) void traj_step_kernel(const TrajParams p, cons
       m = fmax(m, traj_norm(d0, d1, d2));
     }
     m = wave_reduce<RedMax>(m);
-    if (lane == 0) shm[wave] = m;
+    if ((tid & 63) == 0) shm[tid >> 6] = m;         // lane 0 of each wave
     __syncthreads();
     m = waves_combine<RedMax>(shm[0], shm[1], shm[2], shm[3]);
   }
 
-  int state_out = state_in;
-  double kappa = 0.0;
-  if (state_in == 0) {
-    if (bad_total > 0.0) state_out = 2;
-    else if (m < (double)p.tol) state_out = 1;
-    else kappa = m <= (double)p.max_step ? 1.0 : (double)p.max_step / m;
-  }
-  const bool apply = state_in == 0 && state_out == 0;
-
-  if (tid < TREC) {
-    double v = 0.0;
-    if (tid == 2) v = waves_combine<RedMin>(sh[0][2], sh[1][2], sh[2][2], sh[3][2]);
-    else if (tid == 0) v = sum4(0);
-    else if (tid == 1) v = (0.5 * (double)(T - 1)) * sum4(1);
-    else if (tid == 3) v = sum4(3);
-    else if (tid == 4) v = sum4(4);
-    else if (tid == 5) v = sum4(5);
-    else if (tid == 6) v = m;
-    else if (tid == 7) v = kappa;
-    else if (tid == 8) v = bad_total;
-    else if (tid == 9) v = (double)state_out;
-    else if (tid == 10) v = sum4(7);
-    records[b * TREC + tid] = v;
-  }
-  if (tid == 0 && state_out != state_in) state[b] = state_out;
+  const DescentClose cl = descent_close(state_in, bad_total, m, (double)p.tol, (double)p.max_step);
+  descent_record(sh, T, m, bad_total, state_in, cl, 0.0, records + b * DREC, state + b);
 
   // every read of x above is complete: the values went into LDS and registers before the barriers
-  if (!apply && !q_out) return;
+  if (!cl.apply && !q_out) return;
   for (int t = tid; t < T; t += 256) {
     float y0 = xb[t * 3], y1 = xb[t * 3 + 1], y2 = xb[t * 3 + 2];
-    if (apply && t > 0 && t < T - 1) {
-      y0 = (float)((double)y0 + kappa * nab[t]);
-      y1 = (float)((double)y1 + kappa * nab[T + t]);
-      y2 = (float)((double)y2 + kappa * nab[2 * T + t]);
+    if (cl.apply && t > 0 && t < T - 1) {
+      y0 = (float)((double)y0 + cl.kappa * nab[t]);
+      y1 = (float)((double)y1 + cl.kappa * nab[T + t]);
+      y2 = (float)((double)y2 + cl.kappa * nab[2 * T + t]);
       xb[t * 3] = y0; xb[t * 3 + 1] = y1; xb[t * 3 + 2] = y2;
     }
     if (q_out) {

@@ -1266,6 +1266,27 @@ class Engine:
         a.radii = rad.ctypes.data if S else None
         return a, (off, rad), B, T, S
 
+    def _descent_step(self, name, a, var, what, S, state, q, sdf, grad, params, out, q_out, want_grad):
+        """what traj_step and arm_step share: the checks of state, of the field values (with q, the points) against B*T*S, of out
+        and of q_out; the state and the six parameters into `a`.  var [B,T,K]: x or theta, `what` its name.  Returns (the
+        flattened q (if given), sdf and grad, the records, grad_out f64 [B,T,K] or None)."""
+        B, T, K = (int(v) for v in var.shape)
+        if not torch.is_tensor(state) or state.dtype != torch.int32 or state.numel() != B or not state.is_contiguous() \
+                or state.device != var.device:
+            raise ValueError("%s: state must be a contiguous int32 tensor [%d] on %s's device" % (name, B, what))
+        flat = ([] if q is None else [self._flat(q, torch.float32, 3)]) + [self._flat(sdf, torch.float32), self._flat(grad, torch.float32, 3)]
+        n = B * T * S
+        if any(int(v.shape[0]) != n for v in flat):
+            raise ValueError("%s: %d x %d x %d needs %d %ssdf values and gradients (got %s)"
+                             % (name, B, T, S, n, "" if q is None else "points, ", ", ".join(str(int(v.shape[0])) for v in flat)))
+        out = self._record_out(name, out, B, _ffi.TRAJ_RECORD, on=var.device)
+        if q_out is not None and (q_out.dtype != torch.float32 or q_out.numel() != n * 3 or not q_out.is_contiguous()
+                                  or q_out.device != var.device):
+            raise ValueError("%s: q_out must be a contiguous float32 tensor of %d x 3 values on %s's device" % (name, n, what))
+        a.state = _addr(state)
+        a.eps, a.w_obs, a.w_smooth, a.eta, a.max_step, a.tol = (float(v) for v in params)
+        return flat, out, torch.empty(B, T, K, dtype=torch.float64, device=self.device) if want_grad else None
+
     def traj_points(self, x, offsets, radii=0.0):
         """q [B*T*S, 3] f32 on the device: isdf_traj_points, the query points x[b][t] + offsets[s] (one fp32 add per coordinate,
         layout [B][T][S]) of B trajectories of T waypoints whose body is S spheres.  x: contiguous float32 [B,T,3] on the device;
@@ -1288,20 +1309,8 @@ class Engine:
         values that receives the query points of the x the call leaves -- the next field call's input.  One launch, summed
         in a fixed order: the same inputs give the same bytes, whatever else shares the call.  No host synchronisation."""
         a, keep, B, T, S = self._traj_args("traj_step", x, offsets, radii)
-        if not torch.is_tensor(state) or state.dtype != torch.int32 or state.numel() != B or not state.is_contiguous() \
-                or state.device != x.device:
-            raise ValueError("traj_step: state must be a contiguous int32 tensor [%d] on x's device" % B)
-        s, g = self._flat(sdf, torch.float32), self._flat(grad, torch.float32, 3)
-        n = B * T * S
-        if not (s.numel() == int(g.shape[0]) == n):
-            raise ValueError("traj_step: %d x %d x %d needs %d sdf values and gradients (got %d, %d)" % (B, T, S, n, s.numel(), g.shape[0]))
-        out = self._record_out("traj_step", out, B, _ffi.TRAJ_RECORD, on=x.device)
-        if q_out is not None and (q_out.dtype != torch.float32 or q_out.numel() != n * 3 or not q_out.is_contiguous()
-                                  or q_out.device != x.device):
-            raise ValueError("traj_step: q_out must be a contiguous float32 tensor of %d x 3 values on x's device" % n)
-        gout = torch.empty(B, T, 3, dtype=torch.float64, device=self.device) if want_grad else None
-        a.state = _addr(state)
-        a.eps, a.w_obs, a.w_smooth, a.eta, a.max_step, a.tol = (float(v) for v in (eps, w_obs, w_smooth, eta, max_step, tol))
+        (s, g), out, gout = self._descent_step("traj_step", a, x, "x", S, state, None, sdf, grad,
+                                               (eps, w_obs, w_smooth, eta, max_step, tol), out, q_out, want_grad)
         _ffi.check(self.lib.isdf_traj_step(C.byref(a), _addr(s), _addr(g), _ffi.ptr(out),
                                            _ffi.ptr(q_out), _ffi.ptr(gout), _stream(self.device)), "isdf_traj_step")
         return (out, gout) if want_grad else out
@@ -1359,21 +1368,8 @@ class Engine:
         receives the query points of the theta the call leaves -- the next field call's input.  One launch, summed in a fixed
         order: the same inputs give the same bytes, whatever else shares the call.  No host synchronisation."""
         a, keep, B, T, J, S = self._arm_args("arm_step", theta, chain)
-        if not torch.is_tensor(state) or state.dtype != torch.int32 or state.numel() != B or not state.is_contiguous() \
-                or state.device != theta.device:
-            raise ValueError("arm_step: state must be a contiguous int32 tensor [%d] on theta's device" % B)
-        p, s, g = self._flat(q, torch.float32, 3), self._flat(sdf, torch.float32), self._flat(grad, torch.float32, 3)
-        n = B * T * S
-        if not (int(p.shape[0]) == s.numel() == int(g.shape[0]) == n):
-            raise ValueError("arm_step: %d x %d x %d needs %d points, sdf values and gradients (got %d, %d, %d)"
-                             % (B, T, S, n, p.shape[0], s.numel(), g.shape[0]))
-        out = self._record_out("arm_step", out, B, _ffi.TRAJ_RECORD, on=theta.device)
-        if q_out is not None and (q_out.dtype != torch.float32 or q_out.numel() != n * 3 or not q_out.is_contiguous()
-                                  or q_out.device != theta.device):
-            raise ValueError("arm_step: q_out must be a contiguous float32 tensor of %d x 3 values on theta's device" % n)
-        gout = torch.empty(B, T, J, dtype=torch.float64, device=self.device) if want_grad else None
-        a.state = _addr(state)
-        a.eps, a.w_obs, a.w_smooth, a.eta, a.max_step, a.tol = (float(v) for v in (eps, w_obs, w_smooth, eta, max_step, tol))
+        (p, s, g), out, gout = self._descent_step("arm_step", a, theta, "theta", S, state, q, sdf, grad,
+                                                  (eps, w_obs, w_smooth, eta, max_step, tol), out, q_out, want_grad)
         _ffi.check(self.lib.isdf_arm_step(C.byref(a), _addr(p), _addr(s), _addr(g), _ffi.ptr(out), _ffi.ptr(q_out), _ffi.ptr(gout),
                                           _stream(self.device)), "isdf_arm_step")
         return (out, gout) if want_grad else out

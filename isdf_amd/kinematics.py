@@ -27,7 +27,7 @@ import torch
 
 from . import _ffi
 from .planning import (CONVERGED, INVALID, MOVING, REC, PlanResult, TrajStep, _REASON, _engine, _scratch,  # noqa: F401
-                       unpack_records)
+                       best_trajectory, default_field, descend, one_step, unpack_records)
 
 REVOLUTE, PRISMATIC = 0, 1
 # planning.DEFAULTS but for eta: at planning's eta = 8 a float64 host prototype of this loop fell into a period-2 oscillation across
@@ -151,11 +151,7 @@ def _setup(obj, chain, theta, field):
     if theta.dim() != 3 or theta.shape[-1] != chain.J:
         raise ValueError("trajectories must be [B, T, %d] or [T, %d] (got %s)" % (chain.J, chain.J, tuple(theta.shape)))
     theta = theta.detach().to(device=eng.device, dtype=torch.float32).contiguous().clone()
-    if field is None:
-        def field(pts):
-            with torch.no_grad():
-                return eng.sdf_eval(pts, want_grad=True)
-    return eng, theta, field
+    return eng, theta, default_field(eng) if field is None else field
 
 
 def joint_step(engine, chain, theta, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=32.0, max_step=0.05, tol=1e-5, field=None,
@@ -166,14 +162,8 @@ def joint_step(engine, chain, theta, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=32.0,
     joint move before the clamp; records[:, 11] counts the entries of the step a limit cut.  With want_grad also the gradient
     of w_obs F_obs + w_smooth F_smooth, float64 numpy [B,T,J]."""
     eng, th, field = _setup(engine, chain, theta, field)
-    state = torch.zeros(th.shape[0], dtype=torch.int32, device=th.device)
-    q = eng.arm_points(th, chain)
-    sdf, grad = field(q)
-    out = eng.arm_step(th, state, chain, q, sdf, grad, eps=eps, w_obs=w_obs, w_smooth=w_smooth, eta=eta, max_step=max_step, tol=tol,
-                       out=_scratch(th.device).reserve(th.shape[0]), want_grad=want_grad)
-    rec, g = out if want_grad else (out, None)
-    step = unpack_records(_scratch(th.device).fetch(rec))
-    return (step, g.detach().cpu().numpy()) if want_grad else step
+    return one_step(th, lambda: eng.arm_points(th, chain), lambda state, q, sdf, grad, **kw: eng.arm_step(th, state, chain, q, sdf, grad, **kw),
+                    field, want_grad, eps=eps, w_obs=w_obs, w_smooth=w_smooth, eta=eta, max_step=max_step, tol=tol)
 
 
 def optimise_joint_trajectories(engine_or_sdf_map_or_trainer, chain, theta0, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=32.0,
@@ -186,27 +176,8 @@ def optimise_joint_trajectories(engine_or_sdf_map_or_trainer, chain, theta0, eps
     iterations, and at the end, the B x 16 doubles of the last launch are copied once through a pinned buffer, and the loop is
     left when no trajectory is moving any more.  The result does not depend on `check_every`."""
     eng, th, field = _setup(engine_or_sdf_map_or_trainer, chain, theta0, field)
-    B = int(th.shape[0])
-    scratch = _scratch(th.device)
-    rec = scratch.reserve(B)
-    state = torch.zeros(B, dtype=torch.int32, device=th.device)
-    q = eng.arm_points(th, chain)
-    iters, check_every = int(iters), max(1, int(check_every))
-    host, done = None, 0
-    while done < iters:
-        sdf, grad = field(q)
-        eng.arm_step(th, state, chain, q, sdf, grad, eps=eps, w_obs=w_obs, w_smooth=w_smooth, eta=eta, max_step=max_step, tol=tol,
-                     out=rec, q_out=q)
-        done += 1
-        if done % check_every == 0 or done == iters:
-            host = scratch.fetch(rec)
-            if not (host[:, 9] == MOVING).any():
-                break
-    if host is None:                      # iters < 1: nothing was launched
-        host = np.zeros((B, REC))
-    step = unpack_records(host)
-    st = step.state.astype(np.int64)
-    return PlanResult(th, st, [_REASON.get(int(s), "invalid_field") for s in st], done, step)
+    return descend(th, lambda: eng.arm_points(th, chain), lambda state, q, sdf, grad, **kw: eng.arm_step(th, state, chain, q, sdf, grad, **kw),
+                   field, iters, check_every, eps=eps, w_obs=w_obs, w_smooth=w_smooth, eta=eta, max_step=max_step, tol=tol)
 
 
 def seed_joint_trajectories(start, goal, T, n_seeds, spread=0.5, seed=0, lo=None, hi=None):
@@ -246,9 +217,4 @@ def plan_joint_path(obj, chain, start, goal, T=64, n_seeds=32, clearance=0.0, sp
     w_smooth cost_smooth among those whose state is not invalid, that have no sample in collision and whose least clearance is at
     least `clearance`; None if there is none."""
     res = optimise_joint_trajectories(obj, chain, seed_joint_trajectories(start, goal, T, n_seeds, spread, seed, chain.lo, chain.hi), **kw)
-    r = res.records
-    total = kw.get("w_obs", DEFAULTS["w_obs"]) * r.cost_obs + kw.get("w_smooth", DEFAULTS["w_smooth"]) * r.cost_smooth
-    ok = (res.state != INVALID) & (r.in_collision == 0) & (r.min_clearance >= clearance) & np.isfinite(total)
-    if not ok.any():
-        return res, None
-    return res, int(np.argmin(np.where(ok, total, np.inf)))
+    return res, best_trajectory(res, clearance, kw, DEFAULTS)

@@ -109,11 +109,62 @@ def _setup(obj, x, offsets, radii, field):
     rad = np.ascontiguousarray(np.broadcast_to(rad, (off.shape[0],)) if rad.size == 1 else rad)
     if rad.size != off.shape[0]:
         raise ValueError("%d offsets but %d radii" % (off.shape[0], rad.size))
-    if field is None:
-        def field(pts):
-            with torch.no_grad():
-                return eng.sdf_eval(pts, want_grad=True)
-    return eng, x, off, rad, field
+    return eng, x, off, rad, default_field(eng) if field is None else field
+
+
+def default_field(eng):
+    """the engine's own map as a field: device points [N,3] -> `eng.sdf_eval(pts, want_grad=True)`, outside autograd"""
+    def field(pts):
+        with torch.no_grad():
+            return eng.sdf_eval(pts, want_grad=True)
+    return field
+
+
+def one_step(var, points, step, field, want_grad, **params):
+    """trajectory_step and kinematics.joint_step after their set-up: var [B,T,K] the device copy, every trajectory moving;
+    points() -> q, step(state, q, sdf, grad, **kw) the engine's step call on var.  TrajStep, with want_grad also the gradient."""
+    state = torch.zeros(var.shape[0], dtype=torch.int32, device=var.device)
+    q = points()
+    sdf, grad = field(q)
+    out = step(state, q, sdf, grad, out=_scratch(var.device).reserve(var.shape[0]), want_grad=want_grad, **params)
+    rec, g = out if want_grad else (out, None)
+    res = unpack_records(_scratch(var.device).fetch(rec))
+    return (res, g.detach().cpu().numpy()) if want_grad else res
+
+
+def descend(var, points, step, field, iters, check_every, **params):
+    """the loop of optimise_trajectories and kinematics.optimise_joint_trajectories on var [B,T,K], the device copy (points and
+    step as in `one_step`; the step rewrites q in place): PlanResult"""
+    B = int(var.shape[0])
+    scratch = _scratch(var.device)
+    rec = scratch.reserve(B)
+    state = torch.zeros(B, dtype=torch.int32, device=var.device)
+    q = points()
+    iters, check_every = int(iters), max(1, int(check_every))
+    host, done = None, 0
+    while done < iters:
+        sdf, grad = field(q)
+        step(state, q, sdf, grad, out=rec, q_out=q, **params)
+        done += 1
+        if done % check_every == 0 or done == iters:
+            host = scratch.fetch(rec)
+            if not (host[:, 9] == MOVING).any():
+                break
+    if host is None:                      # iters < 1: nothing was launched
+        host = np.zeros((B, REC))
+    res = unpack_records(host)
+    st = res.state.astype(np.int64)
+    return PlanResult(var, st, [_REASON.get(int(s), "invalid_field") for s in st], done, res)
+
+
+def best_trajectory(res, clearance, kw, defaults):
+    """the index of the trajectory of the PlanResult with the lowest w_obs cost_obs + w_smooth cost_smooth (the weights from kw,
+    else from defaults) among those whose state is not invalid, that have no sample in collision and whose least clearance is
+    at least `clearance`; None if there is none"""
+    r = res.records
+    total = kw.get("w_obs", defaults["w_obs"]) * r.cost_obs + kw.get("w_smooth", defaults["w_smooth"]) * r.cost_smooth
+    ok = (res.state != INVALID) & (r.in_collision == 0) & (r.min_clearance >= clearance) & np.isfinite(total)
+    return int(np.argmin(np.where(ok, total, np.inf))) if ok.any() else None
 
 
 def trajectory_step(engine, x, offsets=None, radii=0.0, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=8.0, max_step=0.05, tol=1e-5,
@@ -123,13 +174,8 @@ def trajectory_step(engine, x, offsets=None, radii=0.0, eps=0.2, w_obs=8.0, w_sm
     device points [N,3] -> (sdf [N], grad [N,3]) on the device; default `engine.sdf_eval(pts, want_grad=True)`.  With want_grad
     also the gradient of w_obs F_obs + w_smooth F_smooth, float64 numpy [B,T,3]."""
     eng, xc, off, rad, field = _setup(engine, x, offsets, radii, field)
-    state = torch.zeros(xc.shape[0], dtype=torch.int32, device=xc.device)
-    sdf, grad = field(eng.traj_points(xc, off, rad))
-    out = eng.traj_step(xc, state, off, rad, sdf, grad, eps=eps, w_obs=w_obs, w_smooth=w_smooth, eta=eta, max_step=max_step, tol=tol,
-                        out=_scratch(xc.device).reserve(xc.shape[0]), want_grad=want_grad)
-    rec, g = out if want_grad else (out, None)
-    step = unpack_records(_scratch(xc.device).fetch(rec))
-    return (step, g.detach().cpu().numpy()) if want_grad else step
+    return one_step(xc, lambda: eng.traj_points(xc, off, rad), lambda state, q, sdf, grad, **kw: eng.traj_step(xc, state, off, rad, sdf, grad, **kw),
+                    field, want_grad, eps=eps, w_obs=w_obs, w_smooth=w_smooth, eta=eta, max_step=max_step, tol=tol)
 
 
 def optimise_trajectories(engine_or_sdf_map_or_trainer, x0, offsets=None, radii=0.0, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=8.0,
@@ -144,27 +190,8 @@ def optimise_trajectories(engine_or_sdf_map_or_trainer, x0, offsets=None, radii=
     The defaults are the values at which a float64 host prototype of this loop converged on the analytic room of
     `isdf_amd.synthetic`; they are not tuned on a trained map."""
     eng, x, off, rad, field = _setup(engine_or_sdf_map_or_trainer, x0, offsets, radii, field)
-    B = int(x.shape[0])
-    scratch = _scratch(x.device)
-    rec = scratch.reserve(B)
-    state = torch.zeros(B, dtype=torch.int32, device=x.device)
-    q = eng.traj_points(x, off, rad)
-    iters, check_every = int(iters), max(1, int(check_every))
-    host, done = None, 0
-    while done < iters:
-        sdf, grad = field(q)
-        eng.traj_step(x, state, off, rad, sdf, grad, eps=eps, w_obs=w_obs, w_smooth=w_smooth, eta=eta, max_step=max_step, tol=tol,
-                      out=rec, q_out=q)
-        done += 1
-        if done % check_every == 0 or done == iters:
-            host = scratch.fetch(rec)
-            if not (host[:, 9] == MOVING).any():
-                break
-    if host is None:                      # iters < 1: nothing was launched
-        host = np.zeros((B, REC))
-    step = unpack_records(host)
-    st = step.state.astype(np.int64)
-    return PlanResult(x, st, [_REASON.get(int(s), "invalid_field") for s in st], done, step)
+    return descend(x, lambda: eng.traj_points(x, off, rad), lambda state, q, sdf, grad, **kw: eng.traj_step(x, state, off, rad, sdf, grad, **kw),
+                   field, iters, check_every, eps=eps, w_obs=w_obs, w_smooth=w_smooth, eta=eta, max_step=max_step, tol=tol)
 
 
 def seed_trajectories(start, goal, T, n_seeds, spread=0.5, seed=0):
@@ -197,9 +224,4 @@ def plan_path(obj, start, goal, T=64, n_seeds=32, clearance=0.0, spread=0.5, see
     those whose state is not invalid, that have no sample in collision and whose least clearance is at least `clearance`;
     None if there is none."""
     res = optimise_trajectories(obj, seed_trajectories(start, goal, T, n_seeds, spread, seed), **kw)
-    r = res.records
-    total = kw.get("w_obs", DEFAULTS["w_obs"]) * r.cost_obs + kw.get("w_smooth", DEFAULTS["w_smooth"]) * r.cost_smooth
-    ok = (res.state != INVALID) & (r.in_collision == 0) & (r.min_clearance >= clearance) & np.isfinite(total)
-    if not ok.any():
-        return res, None
-    return res, int(np.argmin(np.where(ok, total, np.inf)))
+    return res, best_trajectory(res, clearance, kw, DEFAULTS)

@@ -182,33 +182,15 @@ def step64(chain, theta, state, q, sdf, grad, eps=0.2, w_obs=8.0, w_smooth=1.0, 
     eps, w_obs, w_smooth, eta, max_step, tol = (float(np.float32(v)) for v in (eps, w_obs, w_smooth, eta, max_step, tol))
     lin = linearise(chain, th32, np.asarray(q, np.float32).reshape(B, T, S, 3), np.asarray(sdf, np.float32).reshape(B, T, S),
                     np.asarray(grad, np.float32).reshape(B, T, S, 3), eps, w_obs, w_smooth)
-    state = np.asarray(state, np.int32).reshape(B)
     lo, hi = limits(chain)
-    rec, scale = np.zeros((B, REC)), np.zeros((B, REC))
-    th_new, state_new = th32.copy(), state.copy()
-    for k, name in ((0, "f_obs"), (1, "f_smooth"), (5, "grad_sq"), (10, "length")):
-        rec[:, k], scale[:, k] = lin[name], lin["scale"][name]
-    rec[:, 2], rec[:, 3], rec[:, 4], rec[:, 8] = lin["min_d"], lin["n_neg"], lin["n_act"], lin["n_bad"]
     th = th32.astype(np.float64)
-    for b in range(B):
-        if state[b] == 0:
-            dp = np.zeros((T, J))
-            delta = -(tm.solve_closed(lin["grad"][b, 1:-1]) / (eta * float(T - 1)))
-            z0 = th[b, 1:-1] + delta
-            z = np.minimum(np.maximum(z0, lo[None]), hi[None])
-            dp[1:-1] = z - th[b, 1:-1]
-            m = float(np.abs(dp).max())
-            rec[b, 6], rec[b, 11] = m, float((z != z0).sum())
-            if lin["n_bad"][b] > 0:
-                state_new[b] = 2
-            elif m < tol:
-                state_new[b] = 1
-            else:
-                kappa = 1.0 if m <= max_step else max_step / m
-                rec[b, 7] = kappa
-                th_new[b, 1:-1] = (th[b, 1:-1] + kappa * dp[1:-1]).astype(np.float32)
-        rec[b, 9] = state_new[b]
-    return rec, scale, lin["grad"], th_new, state_new, lin["grad_scale"]
+
+    def step(b, y):
+        z0 = th[b, 1:-1] + -(y / (eta * float(T - 1)))
+        z = np.minimum(np.maximum(z0, lo[None]), hi[None])
+        dp = z - th[b, 1:-1]
+        return dp, float(np.abs(dp).max()), float((z != z0).sum())
+    return tm.close64(lin, th32, state, max_step, tol, step)
 
 
 def loop64(chain, theta0, field, iters=400, **params):
@@ -229,6 +211,14 @@ def loop64(chain, theta0, field, iters=400, **params):
 def sphere_field(centre=(1.5, 2.5, 1.5), radius=0.5):
     """the single analytic sphere of the gradient test: float64 distance and its exact gradient v / |v|"""
     return tm.sphere_field(centre, radius)
+
+
+class StubEngine(tm.StubEngine):
+    """arm_points and arm_step, computed by this model"""
+
+    def __init__(self):
+        super().__init__("arm", lambda th, chain: points32(chain, th),
+                         lambda th, state, chain, q, sdf, grad, **kw: step64(chain, th, state, q.numpy(), sdf, grad, **kw))
 
 
 # ---- scenes ------------------------------------------------------------------------------------------------------------

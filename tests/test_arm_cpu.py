@@ -2,7 +2,6 @@
 isdf_amd.kinematics' loop driven through a stub engine whose two calls are that model."""
 import numpy as np
 import pytest
-import torch
 
 from isdf_amd import kinematics as kin
 from tests import arm_model as am
@@ -147,34 +146,6 @@ def test_the_model_s_loop_converges_free_of_collision_on_the_exact_room(name):
     assert th[0, [0, -1]].tobytes() == th0[0, [0, -1]].tobytes()
 
 
-class StubEngine:
-    """the two tensor-level calls of isdf_amd.engine.Engine, computed by tests/arm_model.py on the host (CPU tensors, theta and state
-    in place)"""
-
-    def __init__(self):
-        self.device = torch.device("cpu")
-        self.calls = []
-
-    def arm_points(self, theta, chain):
-        self.calls.append(("points", int(theta.shape[0])))
-        return torch.from_numpy(am.points32(chain, theta.numpy()))
-
-    def arm_step(self, theta, state, chain, q, sdf, grad, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=32.0, max_step=0.05, tol=1e-5, out=None,
-                 q_out=None, want_grad=False):
-        rec, _, g, th_new, state_new, _ = am.step64(chain, theta.numpy(), state.numpy(), q.numpy(), sdf.numpy(), grad.numpy(), eps, w_obs,
-                                                    w_smooth, eta, max_step, tol)
-        self.calls.append(("step", int(theta.shape[0])))
-        theta.copy_(torch.from_numpy(th_new))
-        state.copy_(torch.from_numpy(state_new))
-        if q_out is not None:
-            q_out.copy_(torch.from_numpy(am.points32(chain, th_new)).view_as(q_out))
-        rec = torch.from_numpy(rec)
-        if out is not None:
-            out.copy_(rec)
-            rec = out
-        return (rec, torch.from_numpy(g)) if want_grad else rec
-
-
 def test_the_loop_does_not_depend_on_check_every_and_freezes_what_has_stopped():
     """two free bodies, one in free space (converges at its first linearisation) and one through the sphere; the host loop of
     kinematics.optimise_joint_trajectories through the stub engine"""
@@ -184,7 +155,7 @@ def test_the_loop_does_not_depend_on_check_every_and_freezes_what_has_stopped():
     field = tm.host_field(am.sphere_field())
     runs = []
     for every in (1, 7):
-        eng = StubEngine()
+        eng = am.StubEngine()
         res = kin.optimise_joint_trajectories(eng, chain, th0, iters=21, check_every=every, field=field)
         runs.append(res)
         assert eng.calls[0] == ("points", 2) and eng.calls.count(("points", 2)) == 1 and res.iterations == 21
@@ -193,9 +164,9 @@ def test_the_loop_does_not_depend_on_check_every_and_freezes_what_has_stopped():
     assert a.reason == ["converged", "max_iters"] and a.state.tolist() == [1, 0]
     assert a.x.numpy()[0].tobytes() == th0[0].tobytes() and (a.x.numpy()[1, 1:-1] != th0[1, 1:-1]).any()
     assert a.x.numpy()[:, [0, -1]].tobytes() == th0[:, [0, -1]].tobytes()
-    step, g = kin.joint_step(StubEngine(), chain, th0, field=field, want_grad=True)
+    step, g = kin.joint_step(am.StubEngine(), chain, th0, field=field, want_grad=True)
     assert step.in_collision.tolist()[0] == 0 and step.in_collision[1] > 0 and g.shape == (2, 12, 6)
-    res, best = kin.plan_joint_path(StubEngine(), chain, th0[1, 0], th0[1, -1], T=12, n_seeds=3, iters=2, field=field)
+    res, best = kin.plan_joint_path(am.StubEngine(), chain, th0[1, 0], th0[1, -1], T=12, n_seeds=3, iters=2, field=field)
     assert res.x.shape == (3, 12, 6) and (best is None or 0 <= best < 3)
 
 

@@ -132,17 +132,27 @@ def step64(x, state, offsets, radii, sdf, grad, eps=0.2, w_obs=8.0, w_smooth=1.0
     eps, w_obs, w_smooth, eta, max_step, tol = (float(np.float32(v)) for v in (eps, w_obs, w_smooth, eta, max_step, tol))
     lin = linearise(x, np.asarray(sdf, np.float32).reshape(B, T, S), np.asarray(grad, np.float32).reshape(B, T, S, 3), rad, eps,
                     w_obs, w_smooth)
+
+    def step(b, y):
+        delta = -(y / (eta * float(T - 1)))
+        return delta, float(norm3(delta).max()), 0.0
+    return close64(lin, x, state, max_step, tol, step, solve)
+
+
+def close64(lin, var, state, max_step, tol, step, solve=solve_closed):
+    """a step after its linearisation `lin`, for isdf_traj_step and isdf_arm_step alike: the record, the state rule, the clamp
+    factor and the new float32 trajectory.  var float32 [B,T,K]; step(b, y) turns y = solve(grad[b, 1:-1]) into (the step
+    Delta [T-2,K] of the interior rows, its length m, the entries a limit cut).  Returns step64's tuple."""
+    B = var.shape[0]
     state = np.asarray(state, np.int32).reshape(B)
     rec, scale = np.zeros((B, REC)), np.zeros((B, REC))
-    x_new, state_new = x.copy(), state.copy()
+    new, state_new = var.copy(), state.copy()
     for k, name in ((0, "f_obs"), (1, "f_smooth"), (5, "grad_sq"), (10, "length")):
         rec[:, k], scale[:, k] = lin[name], lin["scale"][name]
     rec[:, 2], rec[:, 3], rec[:, 4], rec[:, 8] = lin["min_d"], lin["n_neg"], lin["n_act"], lin["n_bad"]
     for b in range(B):
         if state[b] == 0:
-            delta = np.zeros((T, 3))
-            delta[1:-1] = -(solve(lin["grad"][b, 1:-1]) / (eta * float(T - 1)))
-            m = float(norm3(delta).max())
+            delta, m, rec[b, 11] = step(b, solve(lin["grad"][b, 1:-1]))
             rec[b, 6] = m
             if lin["n_bad"][b] > 0:
                 state_new[b] = 2
@@ -151,9 +161,9 @@ def step64(x, state, offsets, radii, sdf, grad, eps=0.2, w_obs=8.0, w_smooth=1.0
             else:
                 kappa = 1.0 if m <= max_step else max_step / m
                 rec[b, 7] = kappa
-                x_new[b, 1:-1] = (x[b, 1:-1].astype(np.float64) + kappa * delta[1:-1]).astype(np.float32)
+                new[b, 1:-1] = (var[b, 1:-1].astype(np.float64) + kappa * delta).astype(np.float32)
         rec[b, 9] = state_new[b]
-    return rec, scale, lin["grad"], x_new, state_new, lin["grad_scale"]
+    return rec, scale, lin["grad"], new, state_new, lin["grad_scale"]
 
 
 def sphere_field(centre, radius):
@@ -184,27 +194,25 @@ def host_field(fn):
 
 
 class StubEngine:
-    """the two tensor-level calls of isdf_amd.engine.Engine, computed by this model on the host (CPU tensors, x and state in place)"""
+    """the two tensor-level calls of isdf_amd.engine.Engine, `<prefix>_points(var, *body)` and `<prefix>_step(var, state, *body, sdf,
+    grad, ..)`, on the host (CPU tensors, var and state in place): points(var, body[0]) and step, by default this model's step64"""
 
-    def __init__(self):
-        self.device = torch.device("cpu")
-        self.calls = []
+    def __init__(self, prefix="traj", points=points32, step=None):
+        self.device, self.calls = torch.device("cpu"), []
+        self._points, self._step64 = points, step or step64
+        setattr(self, prefix + "_points", self._points_call)
+        setattr(self, prefix + "_step", self._step_call)
 
-    def traj_points(self, x, offsets, radii=0.0):
-        self.calls.append(("points", int(x.shape[0])))
-        return torch.from_numpy(points32(x.numpy(), offsets))
+    def _points_call(self, var, *body):
+        self.calls.append(("points", int(var.shape[0])))
+        return torch.from_numpy(self._points(var.numpy(), body[0]))
 
-    def traj_step(self, x, state, offsets, radii, sdf, grad, eps=0.2, w_obs=8.0, w_smooth=1.0, eta=8.0, max_step=0.05, tol=1e-5,
-                  out=None, q_out=None, want_grad=False):
-        rec, _, g, x_new, state_new, _ = step64(x.numpy(), state.numpy(), offsets, radii, sdf.numpy(), grad.numpy(), eps, w_obs, w_smooth,
-                                                eta, max_step, tol)
-        self.calls.append(("step", int(x.shape[0])))
-        x.copy_(torch.from_numpy(x_new))
+    def _step_call(self, var, state, b0, b1, sdf, grad, out=None, q_out=None, want_grad=False, **params):
+        rec, _, g, new, state_new, _ = self._step64(var.numpy(), state.numpy(), b0, b1, sdf.numpy(), grad.numpy(), **params)
+        self.calls.append(("step", int(var.shape[0])))
+        var.copy_(torch.from_numpy(new))
         state.copy_(torch.from_numpy(state_new))
         if q_out is not None:
-            q_out.copy_(torch.from_numpy(points32(x_new, offsets)).view_as(q_out))
-        rec = torch.from_numpy(rec)
-        if out is not None:
-            out.copy_(rec)
-            rec = out
+            q_out.copy_(torch.from_numpy(self._points(new, b0)).view_as(q_out))
+        rec = torch.from_numpy(rec) if out is None else out.copy_(torch.from_numpy(rec))
         return (rec, torch.from_numpy(g)) if want_grad else rec
