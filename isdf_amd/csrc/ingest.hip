@@ -9,11 +9,23 @@
 // time).  The pass is VALU-bound (nine square roots, five divisions and the argmin with the
 // reference's NaN rule per pixel): 13.1 us per frame with correctly rounded sqrt / division, 9.0 us
 // with the hardware-rate v_sqrt_f32 / v_rcp_f32 (1 ulp) it ships with -- the reference fixture
-// (99.9 % of the pixels within 1e-4) passes either way: profiles/r03_ingest_fastmath.txt.
+// (99.9 % of the pixels within 1e-4) passes either way: profiles/r03_ingest_fastmath.txt.  (Both figures were taken
+// with the products and sums fused; with every one rounded separately, as below, the pass takes 9.2 us.)
 #include "isdf_common.h"
 #include "launchers.h"
 
+// No floating-point contraction in this file.  The toolchain's __fmul_rn / __fadd_rn are plain `*` and `+` that the
+// compiler is free to fuse once they are inlined, and a fused cross product is not the reference's: where both
+// neighbours of the chosen pair are the same point (two zero-depth pixels, i.e. the camera origin twice) the
+// reference's a_y b_z - a_z b_y is exactly 0 and the normal NaN, so the sampler drops the pixel, while
+// fma(a_y, b_z, -(a_z b_y)) is the rounding error of one product and normalises to an arbitrary unit vector
+// (tests/test_ingest_gpu.py, 17x33).  The helpers below are defined under the pragma, so each is one rounded operation.
+#pragma clang fp contract(off)
+
 namespace isdf {
+
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
 
 // hardware-rate square root and reciprocal (1 ulp each): the 1e-4 bar on the normals does not need correct rounding
 __device__ __forceinline__ float n_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
@@ -23,8 +35,8 @@ __device__ __forceinline__ void pix_point(const float* __restrict__ depth, int H
                                           float fy, float cx, float cy, float& x, float& y, float& z) {
   if (i < 0 || i >= H || j < 0 || j >= W) { x = y = z = __int_as_float(0x7fc00000); return; }   // NaN padding
   z = depth[(int64_t)i * W + j];
-  x = n_div(__fmul_rn(z, (float)j - cx), fx);     // transform.py:190-191
-  y = n_div(__fmul_rn(z, (float)i - cy), fy);
+  x = n_div(mul_rn(z, (float)j - cx), fx);     // transform.py:190-191
+  y = n_div(mul_rn(z, (float)i - cy), fy);
 }
 
 // One block = 32 x 16 pixels, two per thread (1 594 blocks for a 680x1200 frame: ONE round on 256 CUs x 8 blocks).  The
@@ -58,12 +70,12 @@ __global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ 
     for (int k = 0; k < 8; ++k) {
       const float x = px[ty + 2 + ly[k]][tx + 2 + lx[k]], y = py[ty + 2 + ly[k]][tx + 2 + lx[k]], z = pz[ty + 2 + ly[k]][tx + 2 + lx[k]];
       qx[k] = x - p1x; qy[k] = y - p1y; qz[k] = z - p1z;
-      len[k] = n_sqrt(__fadd_rn(__fadd_rn(__fmul_rn(qx[k], qx[k]), __fmul_rn(qy[k], qy[k])), __fmul_rn(qz[k], qz[k])));
+      len[k] = n_sqrt(add_rn(add_rn(mul_rn(qx[k], qx[k]), mul_rn(qy[k], qy[k])), mul_rn(qz[k], qz[k])));
     }
     float best = 0.f; int bk = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float s = __fadd_rn(len[k], len[(k + 2) & 7]);
+      float s = add_rn(len[k], len[(k + 2) & 7]);
       if (s != s) s = INFINITY;                       // diff[isnan] = inf, transform.py:259
       if (k == 0 || s < best) { best = s; bk = k; }   // argmin keeps the first minimum
     }
@@ -73,10 +85,10 @@ __global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ 
       if (k == bk) { ax = qx[k]; ay = qy[k]; az = qz[k]; bx = qx[(k + 2) & 7]; by = qy[(k + 2) & 7]; bz = qz[(k + 2) & 7]; }
     }
     // torch.cross then normalise (transform.py:262-267)
-    const float nx = __fadd_rn(__fmul_rn(ay, bz), -__fmul_rn(az, by));
-    const float ny = __fadd_rn(__fmul_rn(az, bx), -__fmul_rn(ax, bz));
-    const float nz = __fadd_rn(__fmul_rn(ax, by), -__fmul_rn(ay, bx));
-    const float nn = n_sqrt(__fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), __fmul_rn(nz, nz)));
+    const float nx = add_rn(mul_rn(ay, bz), -mul_rn(az, by));
+    const float ny = add_rn(mul_rn(az, bx), -mul_rn(ax, bz));
+    const float nz = add_rn(mul_rn(ax, by), -mul_rn(ay, bx));
+    const float nn = n_sqrt(add_rn(add_rn(mul_rn(nx, nx), mul_rn(ny, ny)), mul_rn(nz, nz)));
     float* o = normals + ((int64_t)i * W + j) * 3;
     o[0] = n_div(nx, nn); o[1] = n_div(ny, nn); o[2] = n_div(nz, nn);
   }
@@ -109,7 +121,7 @@ __global__ void render_depth_kernel(const int32_t* __restrict__ n_valid, int64_t
     const float zc = cn >= 0 ? zn : za, sc = s[c];
     int before = 0;                      // samples in front of c in the sorted order
     for (int k = 0; k < S; ++k) before += (z[k] < zc || (z[k] == zc && k < c)) ? 1 : 0;
-    float dpt = __fadd_rn(zc, sc);
+    float dpt = add_rn(zc, sc);
     if (before == S - 1) dpt = 0.f;
     view_depth[r] = dpt;
     if (depth_sample) {
